@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: output tokens/s (whole node) + p50 request latency, Llama-3-8B bf16.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...        (driver form for N > 1)
 
 ``python bench.py --gpus N`` (N > 1) with no launcher environment (WORLD_SIZE unset) launches
@@ -81,6 +81,14 @@ def parse(argv=None):
                     help="self-launched multi-GPU runs (--gpus N > 1 without torchrun): kill every rank and "
                          "exit non-zero after this many seconds")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller: "
+                         "DIR/output_tokens.npy, float32 [requests of the round, gen_len] generated token ids "
+                         "(ids < 2^24 are exact in float32) in submission order; same arguments = same inputs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure (baselines, other "
+                         "configurations, reference comparisons).  A plain run only sets up, warms up, times the "
+                         "steps and prints the result line; there are no such extras today, they belong here")
     ap.add_argument("--trace", default=None, metavar="DIR",
                     help="record a roctx/host/GPU timeline of the timed steps: DIR/trace_rank<r>.json "
                          "(Chrome format) and per-stage device busy %% in the JSON line")
@@ -139,6 +147,20 @@ def emit(args, world, elapsed, lat, extra, global_batch=None):
     if args.json_out:
         with open(args.json_out, "w") as f:
             f.write(line + "\n")
+
+
+def dump_outputs(args, seqs, pipeline_id=0):
+    """``--dump-outputs DIR``: the generated token ids of the last timed round's requests (what
+    ``generate`` hands its caller), in submission order, as one float32 array.  Prompts and weights
+    are seeded by the arguments alone, so two builds run with the same arguments can be compared
+    output for output.  A pipeline other than the first (dp replicas) writes its own file."""
+    if not args.dump_outputs or not seqs:
+        return
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    toks = np.asarray([s.output for s in seqs], dtype=np.float32)
+    name = "output_tokens.npy" if pipeline_id == 0 else f"output_tokens_pipeline{pipeline_id}.npy"
+    np.save(os.path.join(args.dump_outputs, name), toks)
 
 
 def start_trace(args):
@@ -203,6 +225,7 @@ def run_single(args):
              **request_timing(*seq_timing(done))}
     if tr is not None:
         finish_trace(args, tr, elapsed, 0)
+    dump_outputs(args, seqs)
     emit(args, 1, elapsed, lat, extra)
 
 
@@ -364,7 +387,7 @@ def main(argv=None):
         return None
     if world > 1 or args.gpus > 1:
         from distributed_llms_amd.parallel.bench_dist import run_distributed
-        return run_distributed(args, emit, make_prompts, start_trace, finish_trace)
+        return run_distributed(args, emit, make_prompts, start_trace, finish_trace, dump_outputs)
     run_single(args)
 
 

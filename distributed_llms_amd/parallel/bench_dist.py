@@ -19,7 +19,7 @@ def _sync(ctx):
     dist.barrier(group=ctx.ctrl_group)
 
 
-def run_distributed(args, emit, make_prompts, start_trace=None, finish_trace=None):
+def run_distributed(args, emit, make_prompts, start_trace=None, finish_trace=None, dump_outputs=None):
     pp = (getattr(args, "pp", 0) or None) if args.parallelism == "pp" else 1
     tp = getattr(args, "tp", 0) or (int(os.environ.get("WORLD_SIZE", "1")) if args.parallelism == "tp" else 1)
     ctx = init_distributed(pp=pp, tp=tp, moe=getattr(args, "moe", "tp"), timeout_s=600)
@@ -74,6 +74,8 @@ def run_distributed(args, emit, make_prompts, start_trace=None, finish_trace=Non
     hop1 = tp_.hop_stats() if tp_ is not None else {}
     if role.is_driver:
         assert all(len(s.output) == args.gen_len for s in seqs), "incomplete generations"
+        if dump_outputs is not None:        # every pipeline's driver writes its last round's token ids
+            dump_outputs(args, seqs, ctx.pipeline_id)
     # gather latencies to rank 0
     obj = [None] * world
     dist.all_gather_object(obj, (lat, seq_timing(done)), group=ctx.ctrl_group)

@@ -94,6 +94,29 @@ def test_single_process_bench_json_cpu():
     assert rec["ttft_p50_ms"] > 0 and rec["itl_p50_ms"] > 0 and rec["kernel_knobs"] == {}
 
 
+def test_dump_outputs_and_full_cpu(tmp_path):
+    """bench.py --dump-outputs DIR writes the last timed round's generated token ids (float32,
+    [batch, gen_len]); the same arguments give the same inputs and so the same ids, with or without
+    --full (which adds measurements, never changes the headline run); --steps sets the timed rounds."""
+    import numpy as np
+    env = dict(os.environ, OMP_NUM_THREADS="2", PYTHONPATH=ROOT)
+    outs = []
+    for d, more in (("a", []), ("b", ["--full"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup",
+                            "0", "--model", "tiny-llama", "--batch", "3", "--prompt-len", "5", "--gen-len", "4",
+                            "--dump-outputs", str(tmp_path / d)] + more,
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        assert KEYS <= set(lines[0]) and lines[0]["steps"] == 2 and lines[0]["ms_per_step"] > 0
+        assert os.listdir(tmp_path / d) == ["output_tokens.npy"]
+        outs.append(np.load(tmp_path / d / "output_tokens.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (3, 4)
+    assert (outs[0] == np.round(outs[0])).all() and (outs[0] >= 0).all()
+    assert np.array_equal(outs[0], outs[1])
+
+
 def test_open_loop_rate_mode_cpu():
     """bench.py --rate: Poisson arrivals into the running engine; p50 request latency (ms, lower
     is better) with p99 / TTFT / ITL and the offered vs achieved request rate."""

@@ -303,10 +303,13 @@ __global__ void __launch_bounds__(1024) argmax_kernel(int32_t* __restrict__ out,
   __shared__ float sv[16];
   __shared__ int si[16];
   const bf16* row = logits + (size_t)blockIdx.x * row_stride;
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
   const int nvec = ((((uintptr_t)row) & 15) == 0) ? vocab >> 3 : 0;
   const bf16x8* rv = reinterpret_cast<const bf16x8*>(row);
+  // start at the first index this thread visits (0x7fffffff: it visits none), so that element wins
+  // unless a later one is strictly greater: a row of -inf gives index 0, as torch, not the sentinel
+  const int tail0 = nvec * 8 + (int)threadIdx.x;
+  float bv = -INFINITY;
+  int bi = (int)threadIdx.x < nvec ? (int)threadIdx.x * 8 : tail0 < vocab ? tail0 : 0x7fffffff;
   // four 16-byte loads in flight per thread before the first compare (one per iteration left the
   // 250 KB row at ~3.5 TB/s).  A thread visits its indices in increasing order, so inside its scan
   // a strict > keeps the smallest index among equal values (one compare and two selects, not the

@@ -59,11 +59,18 @@ def test_argmax(cuda, rows, vocab):
 @pytest.mark.parametrize("rows,vocab", [(256, 128256), (3, 50257)])
 def test_argmax_ties_take_the_first_index(cuda, rows, vocab):
     """Coarse logits (many equal maxima per row, spread over every thread's strided scan), an
-    all-equal row and a row whose maximum sits in the ragged tail: the first maximal index, as torch."""
+    all-equal row and a row whose maximum sits in the ragged tail: the first maximal index, as torch.
+    Also a row of -inf (index 0), -inf but for one finite value in the ragged tail, and one +inf."""
     logits = (_bf(rows, vocab, scale=3.0).float().round()).to(torch.bfloat16)
     logits[0] = 1.0
     logits[-1, :] = -5.0
     logits[-1, vocab - 3:] = 7.0
+    extra = torch.full((4, vocab), float("-inf"), dtype=torch.bfloat16, device="cuda")
+    extra[0, vocab - 1] = -3.0                  # row 0 is 16-byte aligned: vector scan, then the tail
+    extra[2] = logits[1]
+    extra[2, vocab // 2 + 1] = float("inf")
+    extra[3, vocab - 1] = -3.0                  # with an odd vocab this row is unaligned: scalar scan only
+    logits = torch.cat([extra, logits])
     expect = logits.float().argmax(-1).to(torch.int32)
     torch.testing.assert_close(ops.argmax(logits), expect)
 
@@ -233,13 +240,22 @@ def test_attention_masked_spike(cuda):
     torch.testing.assert_close(out.float(), expect, atol=2e-2, rtol=2e-2)
 
 
-@pytest.mark.parametrize("splits", [3, 5, 6])
+@pytest.mark.parametrize("splits", [3, 4, 5, 6, 8])
 @pytest.mark.parametrize("b", [100, 256])
 def test_decode_rope_consumes_splitk_qkv_bit_exact(cuda, b, splits):
     """The fused decode kernel summing the qkv projection's f32 split-K slabs itself gives exactly
-    the result of reducing first (same slab order, same bf16 rounding)."""
+    the result of reducing first (same slab order, same bf16 rounding): every compiled slab count
+    (3, 4, 5, 8) and the runtime-count kernel (6)."""
+    _splitk_qkv_bit_exact(b, splits, 32, 8, 128, 4096)
+
+
+def test_decode_rope_consumes_splitk_qkv_bit_exact_head_dim_64(cuda):
+    """head_dim 64 (GPT-2 small: N = 2304, K = 768), always the runtime-count kernel."""
+    _splitk_qkv_bit_exact(100, 4, 12, 12, 64, 768)
+
+
+def _splitk_qkv_bit_exact(b, splits, hq, hkv, d, hidden):
     from distributed_llms_amd.ops import gemm
-    hq, hkv, d, hidden = 32, 8, 128, 4096
     lens = [int(x) for x in torch.randint(40, 300, (b,))]
     k, v, bt = _fill_paged(lens, hkv, d)
     x = _bf(b, hidden)
@@ -249,7 +265,7 @@ def test_decode_rope_consumes_splitk_qkv_bit_exact(cuda, b, splits):
     slots = torch.stack([bt[i, (lens[i] - 1) // 32] * 32 + (lens[i] - 1) % 32 for i in range(b)]).to(torch.int32)
     cs = ref.rope_cos_sin(d, 4096, 500000.0, device="cuda")
     part = gemm.linear_wide(x, w, splits=splits, defer=True)
-    assert isinstance(part, gemm.SplitKPartial)
+    assert isinstance(part, gemm.SplitKPartial) and part.splits == splits
     k1, v1, k2, v2 = k.clone(), v.clone(), k.clone(), v.clone()
     o1 = ops.paged_attention_decode_rope(part, pos, cs, k1, v1, slots, bt, sl, hq, hkv, d, 1 / math.sqrt(d))
     qkv = part.materialize()

@@ -17,6 +17,7 @@ PYBIND11_MODULE(_C_kernels, m) {
   m.def("rope_cache_append", &dllm::rope_cache_append);
   m.def("silu_mul", &dllm::silu_mul);
   m.def("argmax", &dllm::argmax);
+  m.def("sample_rows", &dllm::sample_rows);
   m.def("add_inplace", &dllm::add_inplace);
   m.def("moe_route", &dllm::moe_route);
   m.def("moe_grouped_gemm", &dllm::moe_grouped_gemm);

@@ -21,6 +21,10 @@ void rope_cache_append(uintptr_t q_out, uintptr_t qkv, uintptr_t positions, uint
 void silu_mul(uintptr_t out, uintptr_t gu, int tokens, int inter, uintptr_t stream);
 void add_inplace(uintptr_t a, uintptr_t b, long n, uintptr_t stream);
 void argmax(uintptr_t out, uintptr_t logits, int rows, int vocab, long row_stride, uintptr_t stream);
+// sampler.hip: params [rows, 3] i32 (temperature * 1e4, top_k, top_p * 1e4), seeds [rows] u64, pos [rows] i32,
+// uniforms [rows] f32 or 0 (test hook: replaces the Philox draw); all on the device
+void sample_rows(uintptr_t out_ids, uintptr_t logits, int rows, int vocab, long row_stride, uintptr_t params,
+                 uintptr_t seeds, uintptr_t pos, uintptr_t uniforms, uintptr_t stream);
 
 void splitk_add_rms_norm(uintptr_t y, uintptr_t residual, uintptr_t ws, int S, int M, int N, uintptr_t w, float eps,
                          uintptr_t stream);

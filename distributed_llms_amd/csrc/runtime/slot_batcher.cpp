@@ -40,6 +40,7 @@ struct SeqRec {
   int32_t eos = -1;       // < 0: no EOS stop
   int32_t last = 0;       // newest known token
   int32_t samp[3] = {0, 0, 10000};   // temperature * 1e4, top_k, top_p * 1e4
+  int32_t seed[2] = {0, 0};          // low / high word of the 64-bit sampling seed
   bool running = true;
   int reason = R_NONE;
   std::vector<int32_t> out;     // tokens generated while registered here
@@ -60,7 +61,7 @@ class SlotBatcher {
 
   // Register a sequence that finished its prefill and keeps decoding in `slot`.
   void admit(int slot, int64_t id, int32_t len, int32_t last, int32_t remaining, int32_t eos, int32_t temp_e4,
-             int32_t top_k, int32_t top_p_e4) {
+             int32_t top_k, int32_t top_p_e4, int32_t seed_lo, int32_t seed_hi) {
     check_slot(slot);
     if (recs_.count(id)) throw std::invalid_argument("sequence already registered");
     if (remaining <= 0 || len >= max_seq_len_ || len < 1) throw std::invalid_argument("admit: nothing to decode");
@@ -73,6 +74,8 @@ class SlotBatcher {
     r.samp[0] = temp_e4;
     r.samp[1] = top_k;
     r.samp[2] = top_p_e4;
+    r.seed[0] = seed_lo;
+    r.seed[1] = seed_hi;
     recs_.emplace(id, std::move(r));
     order_[slot].push_back(id);
   }
@@ -152,7 +155,7 @@ class SlotBatcher {
     const int b = (int)rows.size();
     bool has_s = false;
     for (int64_t id : rows) has_s |= rec(id).samp[0] > 0;
-    const size_t n = HDR + 3 * (size_t)b + b + (b + 1) + (size_t)b * max_blocks + b + (has_s ? 3 * (size_t)b : 0);
+    const size_t n = HDR + 3 * (size_t)b + b + (b + 1) + (size_t)b * max_blocks + b + (has_s ? 5 * (size_t)b : 0);
     py::array_t<int32_t> packed((py::ssize_t)n);
     int32_t* p = packed.mutable_data();
     std::fill(p, p + HDR, 0);
@@ -164,6 +167,7 @@ class SlotBatcher {
     int32_t* bt = cu + b + 1;
     int32_t* lidx = bt + (size_t)b * max_blocks;
     int32_t* samp = lidx + b;
+    int32_t* seeds = samp + 3 * (size_t)b;    // [b, 2], written whenever samp is (header word 10)
     const int bs = bm_.block_size();
     int32_t max_ctx = 0;
     for (int i = 0; i < b; ++i) {
@@ -182,7 +186,10 @@ class SlotBatcher {
       std::copy(t->begin(), t->end(), row);
       std::fill(row + t->size(), row + max_blocks, 0);
       lidx[i] = i;
-      if (has_s) std::copy(r.samp, r.samp + 3, samp + 3 * (size_t)i);
+      if (has_s) {
+        std::copy(r.samp, r.samp + 3, samp + 3 * (size_t)i);
+        std::copy(r.seed, r.seed + 2, seeds + 2 * (size_t)i);
+      }
       max_ctx = std::max(max_ctx, ctx);
       r.pend += 1;
     }
@@ -196,6 +203,7 @@ class SlotBatcher {
     p[6] = slot;
     p[7] = step_id;
     p[8] = has_s ? 1 : 0;
+    p[10] = has_s ? 1 : 0;   // sample_seeds follow the sampling block
 
     py::array_t<int64_t> rows_a(b);
     std::copy(rows.begin(), rows.end(), rows_a.mutable_data());
@@ -352,7 +360,7 @@ void register_slot_batcher(py::module_& m) {
       .def_property_readonly("max_seq_len", &SlotBatcher::max_seq_len)
       .def("admit", &SlotBatcher::admit, py::arg("slot"), py::arg("seq_id"), py::arg("length"), py::arg("last_token"),
            py::arg("remaining"), py::arg("eos") = -1, py::arg("temp_e4") = 0, py::arg("top_k") = 0,
-           py::arg("top_p_e4") = 10000)
+           py::arg("top_p_e4") = 10000, py::arg("seed_lo") = 0, py::arg("seed_hi") = 0)
       .def("num_running", &SlotBatcher::num_running)
       .def("num_running_total", &SlotBatcher::num_running_total)
       .def("min_running", &SlotBatcher::min_running)

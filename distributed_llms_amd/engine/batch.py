@@ -14,6 +14,7 @@ import torch
 
 from ..models.stage import BatchMeta
 from .scheduler import Step
+from .sequence import split_seed
 
 _FIELDS = ("ids", "positions", "slots", "seq_lens", "cu_seqlens", "block_tables", "logits_idx")
 
@@ -39,6 +40,9 @@ class HostBatch:
     # the packed array this batch was unpacked from (its fields are views into it): pack() then
     # only refreshes the header instead of concatenating everything again
     raw: Optional[np.ndarray] = field(default=None, repr=False, compare=False)
+    # [B, 2] int32: low and high word of each row's 64-bit sampling seed (None: unseeded); packed
+    # after ``sampling`` with header word 10 set
+    sample_seeds: Optional[np.ndarray] = None
 
     @property
     def num_tokens(self) -> int:
@@ -58,20 +62,28 @@ class HostBatch:
         b, t = self.num_seqs, self.num_tokens
         mb = self.block_tables.shape[1] if self.block_tables.ndim == 2 else 0
         has_s = 1 if self.sampling is not None else 0
+        has_seeds = 1 if self.sample_seeds is not None else 0
         hdr = np.array([1 if self.is_prefill else 0, t, b, mb, self.max_q_len, self.max_ctx, self.slot,
-                        self.step_id, has_s, self.num_decode] + [0] * 6, dtype=np.int32)
+                        self.step_id, has_s, self.num_decode, has_seeds] + [0] * 5, dtype=np.int32)
         parts = [hdr, self.ids, self.positions, self.slots, self.seq_lens, self.cu_seqlens,
                  self.block_tables.reshape(-1), self.logits_idx]
         if has_s:
             parts.append(self.sampling.reshape(-1))
+        if has_seeds:
+            parts.append(self.sample_seeds.reshape(-1))
         return np.concatenate([p.astype(np.int32, copy=False).reshape(-1) for p in parts])
 
     def sampling_args(self) -> dict:
         if self.sampling is None:
             return {}
         s = self.sampling
-        return {"temperatures": (s[:, 0] / 1e4).tolist(), "top_k": s[:, 1].tolist(),
+        args = {"temperatures": (s[:, 0] / 1e4).tolist(), "top_k": s[:, 1].tolist(),
                 "top_p": (s[:, 2] / 1e4).tolist()}
+        if self.sample_seeds is not None:
+            # a row draws the token at index seq_lens[row]: the context after this step
+            args["seeds"] = self.sample_seeds
+            args["positions"] = self.seq_lens
+        return args
 
     @staticmethod
     def unpack(arr: np.ndarray) -> "HostBatch":
@@ -88,8 +100,9 @@ class HostBatch:
         bt = take(b * mb).reshape(b, mb)
         lidx = take(b)
         samp = take(3 * b).reshape(b, 3) if has_s else None
+        seeds = take(2 * b).reshape(b, 2) if int(hdr[10]) else None
         return HostBatch(bool(pf), ids, pos, slots, seq_lens, cu, bt, lidx, mq, mc, slot, sid, samp, raw=arr,
-                         num_decode=nd)
+                         num_decode=nd, sample_seeds=seeds)
 
 
 def next_pow2(x: int, lo: int = 1) -> int:
@@ -152,12 +165,13 @@ def build_host_batch(step: Step, bm, block_size: int, max_blocks: Optional[int] 
     bt = np.zeros((b, mb), dtype=np.int32)
     bm.fill_block_tables(seq_ids, bt, 0)
     max_ctx = int(seq_lens.max()) if b else 0
-    sampling = None
+    sampling = seeds = None
     if any(s.params.temperature > 0 for s in seqs):
         sampling = np.array([[int(round(s.params.temperature * 1e4)), int(s.params.top_k),
                               int(round(s.params.top_p * 1e4))] for s in seqs], dtype=np.int32)
+        seeds = np.array([split_seed(s.seed) for s in seqs], dtype=np.int32).reshape(b, 2)
     return HostBatch(step.is_prefill, ids, positions, slots, seq_lens, cu, bt, logits_idx, max_q_len,
-                     max_ctx, step.slot, step_id, sampling)
+                     max_ctx, step.slot, step_id, sampling, sample_seeds=seeds)
 
 
 def merge_mixed(dec: HostBatch, pre: HostBatch, slot: int, step_id: int) -> HostBatch:
@@ -176,12 +190,18 @@ def merge_mixed(dec: HostBatch, pre: HostBatch, slot: int, step_id: int) -> Host
         zp = np.zeros((pre.num_seqs, 3), np.int32)
         sampling = np.concatenate([dec.sampling if dec.sampling is not None else zd,
                                    pre.sampling if pre.sampling is not None else zp])
+    seeds = None
+    if dec.sample_seeds is not None or pre.sample_seeds is not None:
+        seeds = np.concatenate([dec.sample_seeds if dec.sample_seeds is not None else np.zeros((nd, 2), np.int32),
+                                pre.sample_seeds if pre.sample_seeds is not None
+                                else np.zeros((pre.num_seqs, 2), np.int32)]).astype(np.int32)
     return HostBatch(True, np.concatenate([dec.ids, pre.ids]).astype(np.int32),
                      np.concatenate([dec.positions, pre.positions]).astype(np.int32),
                      np.concatenate([dec.slots, pre.slots]).astype(np.int32),
                      np.concatenate([dec.seq_lens, pre.seq_lens]).astype(np.int32), cu, bt,
                      np.concatenate([np.arange(nd, dtype=np.int32), pre.logits_idx.astype(np.int32) + nd]),
-                     max(1, pre.max_q_len), max(dec.max_ctx, pre.max_ctx), slot, step_id, sampling, num_decode=nd)
+                     max(1, pre.max_q_len), max(dec.max_ctx, pre.max_ctx), slot, step_id, sampling, num_decode=nd,
+                     sample_seeds=seeds)
 
 
 def build_decode_batch(seq_ids: np.ndarray, seq_lens: np.ndarray, bm, block_size: int, max_blocks: int,

@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import collections
 import logging
+import os
+import random
 import time
 from typing import Iterable, List, Optional
 
@@ -23,7 +25,7 @@ from .graphs import SCRATCH_SEQ_ID
 from .runner import StageRunner
 from .sampler import sample
 from .scheduler import Scheduler, Step
-from .sequence import SamplingParams, Sequence
+from .sequence import SamplingParams, Sequence, request_seed
 
 log = logging.getLogger("dllm.engine")
 
@@ -75,6 +77,7 @@ class LLMEngine:
         per_slot = -(-ecfg.max_batch // self.num_slots)
         self.scheduler = Scheduler(self.bm, self.num_slots, per_slot, ecfg.max_prefill_tokens, ecfg.max_seq_len,
                                    ecfg.mixed_prefill_tokens)
+        self._seed_rng = random.Random(os.urandom(16))     # seeds of sampled requests that bring none
         self.step_id = 0
         self.num_prefill_tokens = 0
         self.num_decode_tokens = 0
@@ -100,6 +103,7 @@ class LLMEngine:
                     request_id: Optional[str] = None) -> Sequence:
         seq = Sequence(list(prompt), params or SamplingParams(), eos_token_id=self.mcfg.eos_token_id,
                        request_id=request_id)
+        seq.seed = request_seed(seq.params, self._seed_rng)
         self.scheduler.add(seq)
         return seq
 

@@ -1,22 +1,31 @@
 """Token sampling on the last stage.
 
-Greedy rows use the argmax kernel (K10 tail) on bf16 logits; rows with temperature > 0
-use softmax + top-k/top-p + multinomial in torch (fp32).
+Greedy rows use the argmax kernel (K10 tail) on bf16 logits.  With per-row seeds (every batch the
+engines build) the rows with temperature > 0 go through ``ops.sample_rows``: one HIP kernel, a
+stateless Philox draw per (seed, position), so a request's tokens do not depend on its batch, its
+step or a preemption.  Without seeds the rows use softmax + top-k/top-p + multinomial in torch
+(fp32, torch's generator).
 """
 from __future__ import annotations
 
 from typing import Optional, Sequence as Seq
 
+import numpy as np
 import torch
 
 from .. import ops
+from .sequence import split_seed
 
 
 def sample(logits: torch.Tensor, temperatures: Optional[Seq[float]] = None, top_k: Optional[Seq[int]] = None,
-           top_p: Optional[Seq[float]] = None, generator: Optional[torch.Generator] = None) -> torch.Tensor:
-    """logits [B, V] -> ids [B] int32 (device)."""
+           top_p: Optional[Seq[float]] = None, generator: Optional[torch.Generator] = None,
+           seeds=None, positions=None) -> torch.Tensor:
+    """logits [B, V] -> ids [B] int32 (device).  ``seeds`` [B, 2] int32 (low, high words) with
+    ``positions`` [B] (index of the token each row draws): the seeded path."""
     if temperatures is None or all(t <= 0 for t in temperatures):
         return ops.argmax(logits)
+    if seeds is not None:
+        return _sample_seeded(logits, temperatures, top_k, top_p, seeds, positions)
     greedy = ops.argmax(logits)
     temps = torch.tensor([max(t, 1e-5) for t in temperatures], device=logits.device, dtype=torch.float32)
     lf = logits.float() / temps.unsqueeze(1)
@@ -42,9 +51,61 @@ def sample(logits: torch.Tensor, temperatures: Optional[Seq[float]] = None, top_
     return torch.where(is_greedy, greedy, drawn)
 
 
+_STAGE_DEPTH = 4      # pinned buffers per device: more than the steps one slot keeps in flight
+_stages: dict = {}
+
+
+def _stage(host: np.ndarray, device) -> torch.Tensor:
+    """Upload ``host`` (int32) through a small ring of reused pinned buffers instead of pinning a
+    fresh tensor every step.  A buffer is written again only after the copy that last read it has
+    completed (its event; with the ring deeper than the steps in flight that wait is a no-op)."""
+    ring = _stages.setdefault(torch.device(device), {"i": 0, "slots": [None] * _STAGE_DEPTH})
+    i = ring["i"]
+    ring["i"] = (i + 1) % _STAGE_DEPTH
+    slot = ring["slots"][i]
+    n = host.shape[0]
+    if slot is None or slot[0].shape[0] < n:
+        if slot is not None:
+            slot[1].synchronize()
+        slot = ring["slots"][i] = (torch.empty(max(n, 1536), dtype=torch.int32).pin_memory(), torch.cuda.Event())
+    else:
+        slot[1].synchronize()
+    buf, ev = slot
+    buf[:n].numpy()[:] = host
+    dev = buf[:n].to(device, non_blocking=True)
+    ev.record(torch.cuda.current_stream(device))
+    return dev
+
+
+def _sample_seeded(logits, temperatures, top_k, top_p, seeds, positions) -> torch.Tensor:
+    """One staging buffer [params 3B | positions B | seeds 2B] int32, one (pinned, non-blocking on
+    the GPU) copy; the seeds' offset of 4B words keeps them 8-byte aligned."""
+    b = logits.shape[0]
+    if positions is None:
+        raise ValueError("sample: seeds need positions")
+    host = np.empty(6 * b, dtype=np.int32)       # 6 int32 per row: 3 params, 1 position, 2 seed words
+    par = host[:3 * b].reshape(b, 3)
+    par[:, 0] = np.rint(np.asarray(temperatures, dtype=np.float64) * 1e4)
+    par[:, 1] = 0 if top_k is None else np.asarray(top_k)
+    par[:, 2] = 10000 if top_p is None else np.rint(np.asarray(top_p, dtype=np.float64) * 1e4)
+    host[3 * b:4 * b] = np.asarray(positions)
+    host[4 * b:] = np.asarray(seeds, dtype=np.int32).reshape(-1)
+    if logits.is_cuda:
+        t = _stage(host, logits.device)
+    else:
+        t = torch.from_numpy(host)
+    return ops.sample_rows(logits, t[:3 * b].view(b, 3), t[4 * b:].view(torch.int64), t[3 * b:4 * b])
+
+
 def step_sampling_args(seqs) -> dict:
+    """``sample`` arguments of a step over ``seqs``, as ``HostBatch.sampling_args()`` gives them
+    for the step's batch.  A row draws the token at the index its context reaches in this step:
+    the end of its chunk for a chunked prefill row, else its whole length (prefill and decode)."""
     temps = [s.params.temperature for s in seqs]
     if all(t <= 0 for t in temps):
         return {}
     return {"temperatures": temps, "top_k": [s.params.top_k for s in seqs],
-            "top_p": [s.params.top_p for s in seqs]}
+            "top_p": [s.params.top_p for s in seqs],
+            "seeds": np.array([split_seed(s.seed) for s in seqs], dtype=np.int32).reshape(len(seqs), 2),
+            "positions": np.array([s.num_cached + s.chunk if s.chunk else s.total_len for s in seqs],
+                                  dtype=np.int32)}

@@ -20,7 +20,7 @@ from typing import Deque, Dict, List, Optional
 import numpy as np
 
 from .. import _ext
-from .sequence import Sequence, SeqStatus
+from .sequence import Sequence, SeqStatus, split_seed
 
 
 class Step:
@@ -341,7 +341,7 @@ class Scheduler:
             self.native.admit(step.slot, seq.seq_id, seq.total_len, seq.output[-1],
                               p.max_new_tokens - len(seq.output), _eos_of(seq),
                               int(round(p.temperature * 1e4)) if p.temperature > 0 else 0, int(p.top_k),
-                              int(round(p.top_p * 1e4)))
+                              int(round(p.top_p * 1e4)), *split_seed(seq.seed))
             self.live[seq.seq_id] = seq
         return done
 

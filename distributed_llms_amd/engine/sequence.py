@@ -40,6 +40,25 @@ class SamplingParams:
 
 _ids = itertools.count(1)
 
+SEED_MASK = (1 << 64) - 1
+
+
+def request_seed(params: SamplingParams, rng) -> int:
+    """The seed a request samples with: the user's, masked to 64 bits, or one drawn from ``rng``
+    (a ``random.Random``) once per request; greedy requests need none."""
+    if params.temperature <= 0:
+        return 0
+    if params.seed is None:
+        return rng.getrandbits(64)
+    return int(params.seed) & SEED_MASK
+
+
+def split_seed(seed: int):
+    """A 64-bit seed as (low, high) signed 32-bit words, the wire form of ``HostBatch.sample_seeds``."""
+    def i32(w):
+        return (w ^ 0x80000000) - 0x80000000
+    return i32(seed & 0xFFFFFFFF), i32((seed >> 32) & 0xFFFFFFFF)
+
 
 @dataclass
 class Sequence:
@@ -58,6 +77,9 @@ class Sequence:
     finish_time: Optional[float] = None
     token_times: List[float] = field(default_factory=list)
     finish_reason: Optional[str] = None
+    # the 64-bit sampling seed of the request (request_seed), fixed at admission: preemption,
+    # chunked prefill and recompute draw token n from Philox(seed, n) again
+    seed: int = 0
 
     def __post_init__(self):
         if not self.prompt:

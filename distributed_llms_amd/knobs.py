@@ -101,6 +101,11 @@ class Knobs:
     defer_o: bool = True              # split-K o-proj reduce fused into the next add + RMSNorm
     lookahead: bool = True            # single-GPU engine: issue step n+1 before step n's tokens land
     pp_lookahead: bool = True         # pipeline driver: the same across stages
+    # seeded sampling (temperature / top-k / top-p / Philox draw) in one HIP kernel behind the LM
+    # head (csrc/kernels/sampler.hip; cost against ops.argmax and the torch chain of
+    # engine/sampler.py: profiles/sampler.md).  False: seeded rows take ops/reference.py
+    # sample_rows, the same contract in numpy on the host
+    fused_sampler: bool = True
     # RCCL transport comm streams (send / recv / ring / ids copy): "pool" (torch pool streams) or
     # "priority" (one native high-priority stream per role: a queue of its own, but a spinning
     # high-priority kernel starves the compute queues -- pp2 73 % of IPC, pp4 stalled;

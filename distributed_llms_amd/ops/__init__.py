@@ -24,7 +24,7 @@ __all__ = [
     "embedding", "rms_norm", "fused_add_rms_norm", "layer_norm", "linear", "silu_mul",
     "gelu_tanh", "rope_cache_append", "paged_attention_decode", "paged_attention_prefill",
     "argmax", "add_", "moe_route", "moe_mlp", "decode_split_plan", "paged_attention_decode_rope",
-    "paged_attention_prefill_rope",
+    "paged_attention_prefill_rope", "sample_rows",
 ]
 
 
@@ -453,6 +453,59 @@ def argmax(logits: torch.Tensor) -> torch.Tensor:
     rows, v = logits.shape
     out = torch.empty(rows, dtype=torch.int32, device=logits.device)
     _ext.kernels().argmax(out.data_ptr(), logits.data_ptr(), rows, v, logits.stride(0), _stream())
+    return out
+
+
+SAMPLE_MAX_VOCAB = 131072      # csrc/kernels/sampler.hip: 16 groups of 8 entries per thread, 1024 threads
+_host_sampler_warned = False
+
+
+def _warn_host_sampler(logits: torch.Tensor) -> None:
+    """Once per process: GPU logits are about to be sampled by the host reference."""
+    global _host_sampler_warned
+    if not _host_sampler_warned:
+        _host_sampler_warned = True
+        import logging
+        logging.getLogger("dllm.ops").warning(
+            "sample_rows: %s logits on %s take the host reference (knobs.fused_sampler=%s): the [B, V] logits are "
+            "copied to the host every step, which synchronises the device and cannot be graph-captured",
+            logits.dtype, logits.device, knobs.K.fused_sampler)
+
+
+def sample_rows(logits: torch.Tensor, params: torch.Tensor, seeds: torch.Tensor, pos: torch.Tensor,
+                uniforms: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Seeded temperature / top-k / top-p sampling, one id per row (contract: ops/reference.py).
+
+    logits [B, V]; params [B, 3] int32 (temperature * 1e4, top_k, top_p * 1e4); seeds [B] int64
+    (the 64-bit seed's bit pattern); pos [B] int32 (index of the token being drawn); uniforms [B]
+    float32 or None (test hook: replaces the Philox draw).  Every per-row value is read on the
+    device: no host synchronisation, graph-capturable.  bf16 CUDA logits with a contiguous last dim
+    (at most SAMPLE_MAX_VOCAB entries) take the HIP kernel; anything else, and everything with
+    ``knobs.fused_sampler`` off, the reference -- numpy on the host, so GPU logits then cost a
+    device-to-host copy and a synchronisation per step (logged once)."""
+    if not (_gpu(logits) and logits.dtype == torch.bfloat16 and logits.stride(-1) == 1 and knobs.K.fused_sampler):
+        if _gpu(logits):
+            _warn_host_sampler(logits)
+        return ref.sample_rows(logits, params, seeds, pos, uniforms)
+    rows, v = logits.shape
+    if v > SAMPLE_MAX_VOCAB:
+        raise ValueError(f"sample_rows: vocab {v} exceeds the kernel's register-resident row of {SAMPLE_MAX_VOCAB}")
+    dev = logits.device
+    _ck(params, "sample_rows.params", torch.int32)
+    _ck(seeds, "sample_rows.seeds", torch.int64)
+    _ck(pos, "sample_rows.pos", torch.int32)
+    if params.shape != (rows, 3) or seeds.shape != (rows,) or pos.shape != (rows,):
+        raise ValueError(f"sample_rows: params / seeds / pos must be [{rows}, 3] / [{rows}] / [{rows}]")
+    if uniforms is not None:
+        _ck(uniforms, "sample_rows.uniforms", torch.float32)
+        if uniforms.shape != (rows,):
+            raise ValueError(f"sample_rows: uniforms must be [{rows}]")
+    if any(t.device != dev for t in (params, seeds, pos) + (() if uniforms is None else (uniforms,))):
+        raise ValueError("sample_rows: params, seeds, pos and uniforms must be on the logits' device")
+    out = torch.empty(rows, dtype=torch.int32, device=dev)
+    _ext.kernels().sample_rows(out.data_ptr(), logits.data_ptr(), rows, v, logits.stride(0), params.data_ptr(),
+                               seeds.data_ptr(), pos.data_ptr(), 0 if uniforms is None else uniforms.data_ptr(),
+                               _stream())
     return out
 
 

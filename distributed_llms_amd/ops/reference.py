@@ -226,6 +226,120 @@ def argmax(logits: torch.Tensor) -> torch.Tensor:
     return logits.float().argmax(dim=-1).to(torch.int32)
 
 
+# ------------------------------------------------------------------ seeded sampling
+# The contract of csrc/kernels/sampler.hip, in numpy with float64 masses.  Per row: int32 params
+# (temp_e4, top_k, top_p_e4), a 64-bit seed and pos, the index of the token being drawn.
+#   temp_e4 <= 0  the argmax (first index on ties; NaN counts as -inf; an all -inf row gives 0)
+#   otherwise     x = l / T with T = temp_e4 * 1e-4, w = exp(x - x_max)
+#     top-k  (0 < k < V)  keep x >= the k-th largest value; ties at the threshold are all kept
+#     top-p  over the top-k survivors keep value v iff mass{x > v} <= p * Z_k (whole tie groups)
+#     draw   u = (philox4x32_10((pos, 0, 0, 0), (seed_lo, seed_hi))[0] >> 8) * 2^-24; the first
+#            kept index, in token order, whose inclusive cumulative kept mass exceeds u * Z_kept
+#            (the last kept index if rounding leaves none).  ``uniforms`` (test hook) replaces u,
+#            truncated to a multiple of 2^-24 below 1.
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10.  ctr [..., 4], key [..., 2] (anything numpy turns into uint32 words; they
+    broadcast against each other) -> uint32 [..., 4]."""
+    import numpy as np
+    c = np.asarray(ctr, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    k = np.asarray(key, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).copy() for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).copy() for i in range(2))
+    mask, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    for _ in range(10):
+        p0 = np.uint64(_PHILOX_M0) * c0
+        p1 = np.uint64(_PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & mask, (p0 >> s32) ^ c3 ^ k1, p0 & mask
+        k0 = (k0 + np.uint64(_PHILOX_W0)) & mask
+        k1 = (k1 + np.uint64(_PHILOX_W1)) & mask
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def sample_uniforms(seeds, pos):
+    """u in [0, 1) float64 of (seed, pos) pairs; seeds: 64-bit ints (any sign), pos: ints."""
+    import numpy as np
+    s = np.asarray(seeds).astype(np.int64).view(np.uint64).reshape(-1)
+    p = np.asarray(pos).astype(np.int64).reshape(-1)
+    ctr = np.zeros((p.shape[0], 4), dtype=np.uint64)
+    ctr[:, 0] = p.view(np.uint64) & np.uint64(0xFFFFFFFF)
+    key = np.stack([s & np.uint64(0xFFFFFFFF), s >> np.uint64(32)], axis=-1)
+    return (philox4x32_10(ctr, key)[:, 0] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+
+
+def sample_rows_detail(logits, params, u, dtype=None):
+    """The contract on numpy arrays: logits [B, V] floats, params [B, 3] ints, u [B] float64 ->
+    (ids int32 [B], kept bool [B, V], w [B, V]).  ``kept`` / ``w`` of greedy rows and of rows
+    without an entry above -inf are not meaningful.  ``dtype``: the type of the masses and their
+    sums (float64; float32 is how tests measure what single precision costs)."""
+    import numpy as np
+    dtype = np.float64 if dtype is None else dtype
+    l = np.array(logits, dtype=dtype)
+    params = np.asarray(params, dtype=np.int64)
+    b, v = l.shape
+    l[np.isnan(l)] = -np.inf
+    lmax = l.max(axis=1)
+    first_max = np.argmax(l, axis=1)
+    rows = np.arange(b)[:, None]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        t = (np.where(params[:, 0] > 0, params[:, 0], 1) * 1e-4).astype(dtype)
+        d = l - lmax[:, None]
+        d[l == lmax[:, None]] = 0.0          # inf - inf at a +inf maximum
+        x = d / t[:, None]
+        w = np.exp(x)
+        order = np.argsort(-x, axis=1, kind="stable")
+        xs = np.take_along_axis(x, order, 1)
+        k = params[:, 1]
+        kact = (k > 0) & (k < v)
+        tau_k = xs[np.arange(b), np.clip(k, 1, v) - 1]
+        keep = np.where(kact[:, None], x >= tau_k[:, None], True)
+        zk = (w * keep).sum(axis=1)
+        # mass strictly above each value, in sorted order: the cumulative mass before its tie group
+        ws = np.take_along_axis(w * keep, order, 1)
+        cum = np.cumsum(ws, axis=1)
+        pos = np.broadcast_to(np.arange(v), (b, v))
+        new_group = np.concatenate([np.ones((b, 1), dtype=bool), xs[:, 1:] != xs[:, :-1]], axis=1)
+        start = np.maximum.accumulate(np.where(new_group, pos, 0), axis=1)
+        excl = np.concatenate([np.zeros((b, 1), dtype=dtype), cum], axis=1)
+        above_s = np.take_along_axis(excl, start, 1)
+        p = (np.clip(params[:, 2], 0, 10000) * 1e-4).astype(dtype)
+        keep_ps = np.where((params[:, 2] < 10000)[:, None], above_s <= (p * zk)[:, None], True)
+        keep_p = np.empty_like(keep_ps)
+        np.put_along_axis(keep_p, order, keep_ps, 1)
+        kept = keep & keep_p
+        mk = w * kept
+        cdf = np.cumsum(mk, axis=1)
+        z = cdf[:, -1]
+        hit = cdf > (np.asarray(u, dtype=np.float64).astype(dtype) * z)[:, None]
+        drawn = np.where(hit.any(axis=1), hit.argmax(axis=1), v - 1 - kept[:, ::-1].argmax(axis=1))
+    ids = np.where((params[:, 0] <= 0) | np.isneginf(lmax), first_max, drawn)
+    return ids.astype(np.int32), kept, w
+
+
+def sample_rows(logits: torch.Tensor, params: torch.Tensor, seeds: torch.Tensor, pos: torch.Tensor,
+                uniforms: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """logits [B, V]; params [B, 3] int32; seeds [B] int64 (the 64-bit pattern); pos [B] int32;
+    uniforms [B] float32 or None -> ids [B] int32 on the logits' device."""
+    import numpy as np
+    lg = logits.detach().float().cpu().numpy()
+    b, v = lg.shape
+    pr = params.detach().cpu().numpy().reshape(b, 3)
+    if uniforms is None:
+        u = sample_uniforms(seeds.detach().cpu().numpy(), pos.detach().cpu().numpy())
+    else:
+        m = np.floor(np.clip(uniforms.detach().float().cpu().numpy().astype(np.float64), 0.0, 1.0) * 2.0 ** 24)
+        u = np.minimum(m, 2.0 ** 24 - 1) * 2.0 ** -24
+    ids = np.empty(b, dtype=np.int32)
+    step = max(1, (1 << 22) // max(v, 1))         # bound the float64 temporaries
+    for s in range(0, b, step):
+        ids[s:s + step] = sample_rows_detail(lg[s:s + step], pr[s:s + step], u[s:s + step])[0]
+    return torch.from_numpy(ids).to(logits.device)
+
+
 def moe_route(router_logits: torch.Tensor, top_k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Mixtral routing: softmax over experts, top-k, renormalise. -> (weights f32, ids i32)."""
     probs = torch.softmax(router_logits.float(), dim=-1)

@@ -24,6 +24,7 @@ from __future__ import annotations
 import collections
 import logging
 import os
+import random
 import time
 from typing import Deque, List, Optional
 
@@ -36,7 +37,7 @@ from ..engine.batch import HostBatch, build_host_batch
 from ..engine.runner import StageRunner
 from ..engine.sampler import sample
 from ..engine.scheduler import Scheduler, Step
-from ..engine.sequence import SamplingParams, Sequence
+from ..engine.sequence import SamplingParams, Sequence, request_seed
 from ..utils.tracing import get_tracer
 from .comm import STOP, PendingIds, Transport
 
@@ -119,6 +120,7 @@ class PipelineDriver:
         self.lookahead = knobs.K.pp_lookahead
         # pp x tp: the stage-0 TP peers replay every issue on their own lanes
         self.tp = runner.stage.tp if runner.stage.tp.enabled else None
+        self._seed_rng = random.Random(os.urandom(16))     # seeds of sampled requests that bring none
         self.step_id = 0
         self.num_steps = 0
         self.num_lookahead = 0
@@ -128,6 +130,7 @@ class PipelineDriver:
                     request_id: Optional[str] = None) -> Sequence:
         seq = Sequence(list(prompt), params or SamplingParams(), eos_token_id=self.mcfg.eos_token_id,
                        request_id=request_id)
+        seq.seed = request_seed(seq.params, self._seed_rng)
         self.scheduler.add(seq)
         return seq
 

@@ -143,7 +143,8 @@ def tp_sample(logits_local: torch.Tensor, tp: TPGroup, sampling_args: dict) -> t
 
     Greedy: each rank's local argmax (value, global index) is all-gathered and reduced with the
     same tie rule as the argmax kernel (largest value, then smallest index).  Otherwise the full
-    logits are gathered and the leader's draw is broadcast (one sampler, one RNG stream)."""
+    logits are gathered and the leader's draw is broadcast (one sampler; ``sampling_args`` carries
+    the rows' seeds and positions through to it, engine/sampler.py)."""
     from ..engine.sampler import sample
     from .. import ops
     b, v_l = logits_local.shape

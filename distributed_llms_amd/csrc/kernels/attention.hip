@@ -18,11 +18,6 @@
 namespace dllm {
 
 constexpr int kBS = 32;       // tokens per KV block (== keys per MFMA chunk)
-#ifndef DLLM_VFULL
-#define DLLM_VFULL 1
-#endif
-// fused decode appends v by rewriting its key group's whole V^T tile (see patch() below)
-constexpr bool kVFullLines = DLLM_VFULL;
 constexpr int kWaves = 4;     // waves per workgroup
 typedef __attribute__((address_space(3))) void* lds_vptr_a;
 typedef __attribute__((address_space(1))) void* glb_vptr_a;
@@ -224,24 +219,31 @@ __device__ __forceinline__ bf16 qkv_load1(const RopeArgs& ra, int b, int width, 
   return f2bf(a);
 }
 
-template <int D, bool FUSED>
-__device__ __forceinline__ void rope_rotate(bf16x8 (&f)[D / 32], const float* cs, int g) {
-  if (cs == nullptr) return;
+// Rotate-half RoPE on one lane's NF fragments of a head (D = NF * STEP dims): fragment ks holds the
+// 8 dims STEP * ks + lane offset + 0..7, so the partners (e, e + D/2) are fragments ks and ks + NF/2 of
+// the same lane.  cs_lane: the position's cos / sin row (first half cos, second half sin) plus the lane
+// offset -- 8 g in the 16x16 layout (NF = D/32, STEP = 32), 8 hi in the 32x32 one (NF = 8, STEP = 16) --
+// or null for no rotation.  (The null test stays in here, once per call: one test around the fused
+// decode's two calls merged their blocks and changed that kernel's schedule and register count.)
+template <int NF, int STEP>
+__device__ __forceinline__ void rope_rotate(bf16x8 (&f)[NF], const float* cs_lane) {
+  constexpr int D = NF * STEP;
+  if (cs_lane == nullptr) return;
 #pragma unroll
-  for (int ks = 0; ks < D / 64; ++ks) {
-    const f32x4 c0 = *reinterpret_cast<const f32x4*>(cs + ks * 32 + 8 * g);
-    const f32x4 c1 = *reinterpret_cast<const f32x4*>(cs + ks * 32 + 8 * g + 4);
-    const f32x4 s0 = *reinterpret_cast<const f32x4*>(cs + D / 2 + ks * 32 + 8 * g);
-    const f32x4 s1 = *reinterpret_cast<const f32x4*>(cs + D / 2 + ks * 32 + 8 * g + 4);
+  for (int ks = 0; ks < NF / 2; ++ks) {
+    const f32x4 c0 = *reinterpret_cast<const f32x4*>(cs_lane + STEP * ks);
+    const f32x4 c1 = *reinterpret_cast<const f32x4*>(cs_lane + STEP * ks + 4);
+    const f32x4 s0 = *reinterpret_cast<const f32x4*>(cs_lane + D / 2 + STEP * ks);
+    const f32x4 s1 = *reinterpret_cast<const f32x4*>(cs_lane + D / 2 + STEP * ks + 4);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float c = j < 4 ? c0[j] : c1[j - 4], s = j < 4 ? s0[j] : s1[j - 4];
-      const float a = bf2f(f[ks][j]), b = bf2f(f[ks + D / 64][j]);
+      const float a = bf2f(f[ks][j]), b = bf2f(f[ks + NF / 2][j]);
       // explicit FMAs: left to hipcc's default contraction, the fused / unfused choice here may
       // differ between kernel instantiations, and the bf16-qkv and split-K-slab forms of the fused
       // decode must rotate q / k bit-identically (a trial build rotated them 1 ulp apart at times)
       f[ks][j] = f2bf(__builtin_fmaf(a, c, -(b * s)));
-      f[ks + D / 64][j] = f2bf(__builtin_fmaf(b, c, a * s));
+      f[ks + NF / 2][j] = f2bf(__builtin_fmaf(b, c, a * s));
     }
   }
 }
@@ -304,9 +306,9 @@ __global__ void __launch_bounds__(WPB * 64, 2) attn_decode_kernel(   // 2nd arg:
   auto finish_rope = [&]() {
     if (!FUSED || rope_done) return;
     rope_done = true;
-    const float* cs = ra.cos_sin ? ra.cos_sin + (size_t)pos_b * D : nullptr;   // pos_b: loaded first
-    rope_rotate<D, FUSED>(qf, cs, g);
-    rope_rotate<D, FUSED>(kn, cs, g);
+    const float* cs = ra.cos_sin ? ra.cos_sin + (size_t)pos_b * D + 8 * g : nullptr;   // pos_b: loaded first
+    rope_rotate<D / 32, 32>(qf, cs);
+    rope_rotate<D / 32, 32>(kn, cs);
     if (!col_ok) {
 #pragma unroll
       for (int ks = 0; ks < D / 32; ++ks) qf[ks] = bf16x8{};
@@ -336,16 +338,14 @@ __global__ void __launch_bounds__(WPB * 64, 2) attn_decode_kernel(   // 2nd arg:
     for (int dt = 0; dt < D / 16; ++dt)
 #pragma unroll
       for (int i = 0; i < 8; ++i) c.v[dt][i] = (vcol && i == e) ? vn[dt] : c.v[dt][i];
-    if constexpr (kVFullLines) {
-      // append v as WHOLE lines: the 16 lanes of the new key's group hold the group's complete
-      // [D][8] V^T tile (2 KiB, 16 full 128-B lines) with the new key patched in -- no partially
-      // written lines to read-modify-write.  This is the sequence's last chunk: no KV load follows
-      // whose vmcnt wait would include these stores.
-      if (vcol && owns_new) {
+    // append v as WHOLE lines: the 16 lanes of the new key's group hold the group's complete
+    // [D][8] V^T tile (2 KiB, 16 full 128-B lines) with the new key patched in -- no partially
+    // written lines to read-modify-write.  This is the sequence's last chunk: no KV load follows
+    // whose vmcnt wait would include these stores.
+    if (vcol && owns_new) {
 #pragma unroll
-        for (int dt = 0; dt < D / 16; ++dt)
-          *reinterpret_cast<bf16x8*>(v_cache + cbase + g * 8 * D + (dt * 16 + r) * 8) = c.v[dt];
-      }
+      for (int dt = 0; dt < D / 16; ++dt)
+        *reinterpret_cast<bf16x8*>(v_cache + cbase + g * 8 * D + (dt * 16 + r) * 8) = c.v[dt];
     }
   };
   WaveState<D> st;
@@ -385,10 +385,11 @@ __global__ void __launch_bounds__(WPB * 64, 2) attn_decode_kernel(   // 2nd arg:
   }
   finish_rope();   // no cache chunk in this split
   if (owns_new) {
-    // append k (row krow32(off)) and v (its [4][D][8] V^T slots) to the paged cache only now, after the
-    // last KV load: stores count in vmcnt in issue order, so stores issued before the KV stream
-    // made every later chunk wait for their (scattered 2-byte V^T) write acknowledgements
-    // (cold microbench, B=256 ctx 192: 47.8 us fused vs 38.8 us attention alone)
+    // append k (row krow32(off)) to the paged cache only now, after the last KV load (v went out as
+    // whole lines in patch(), behind the last load as well): stores count in vmcnt in issue order, so
+    // stores issued before the KV stream made every later chunk wait for their write acknowledgements
+    // -- k's and, then, v's scattered 2-byte V^T slots (cold microbench, B=256 ctx 192: 47.8 us fused
+    // vs 38.8 us attention alone)
     const int slot = ra.slots[b];
     const int blk = slot / kBS, off = slot % kBS;
     const size_t base = ((size_t)blk * hkv + kvh) * kBS * D;
@@ -396,10 +397,6 @@ __global__ void __launch_bounds__(WPB * 64, 2) attn_decode_kernel(   // 2nd arg:
 #pragma unroll
       for (int ks = 0; ks < D / 32; ++ks)
         *reinterpret_cast<bf16x8*>(k_cache + base + (size_t)krow32(off) * D + ks * 32 + 8 * g) = kn[ks];
-    }
-    if (!kVFullLines && g == 0) {
-#pragma unroll
-      for (int dt = 0; dt < D / 16; ++dt) v_cache[base + vofs(off, dt * 16 + r, D, kBS)] = vn[dt];
     }
   }
   float lt = st.lsum;
@@ -449,11 +446,51 @@ __global__ void __launch_bounds__(D) attn_split_reduce_kernel(bf16* __restrict__
 // ---------------------------------------------------------------------------
 // Prefill (causal, varlen, context already in the paged cache): grid (q_tiles, Hkv, B); each wave
 // owns 16/G query rows x G heads per column tile, the rows of sequence b being its LAST q_len tokens
-// of ctx (chunked prefill).  Two kernels remain: the LDS-shared v4 below (default) and v3 here, its
-// fallback beyond the 32k tokens of block ids v4 stages.  The first design (v1: one tile per wave,
+// of ctx (chunked prefill).  Two 16x16 kernels remain: the LDS-shared v4 below (default for short
+// prompts) and v3 here, the fallback beyond the 32k tokens of block ids the LDS kernels stage; long
+// prompts take the 32x32 kernels v7 / v9 further below.  The first design (v1: one tile per wave,
 // load -> compute per chunk, 563 us per 8B layer for 256 x 128-token prompts), v2 at one tile per
 // wave and v4 at four tiles per wave (one wave per SIMD, slower) were measured and removed.
 // ---------------------------------------------------------------------------
+// One 16-column tile's output straight from the accumulators (16/G query rows from trow0 x G heads):
+// a lane holds 4 dims of one column per fragment, so a store instruction writes 32 bytes into each
+// of 16 rows.  v3's epilogue, and v4's where its LDS output image does not fit.
+template <int D, int G>
+__device__ __forceinline__ void store_tile_direct(bf16* __restrict__ out, const WaveState<D>& st, int trow0, int qs,
+                                                  int ql, int hq, int kvh, int lane) {
+  const int r = lane & 15, g = lane >> 4;
+  float lt = st.lsum;
+  lt = rows_sum(lt);
+  const int crow = trow0 + r / G, ch = r % G;
+  if (crow < ql) {
+    const float inv = lt > 0.f ? 1.f / lt : 0.f;
+    bf16* orow = out + ((size_t)(qs + crow) * hq + kvh * G + ch) * D;
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) {
+      bf16x4 o;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[i] = f2bf(st.acc[dt][i] * inv);
+      *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * g) = o;
+    }
+  }
+}
+
+// XCD-aware order: workgroups are dealt round-robin to the 8 XCDs in dispatch order, so the
+// gridDim.x row tiles of one (sequence, kv head) -- which stream the same K / V chunks -- would
+// land on gridDim.x different XCDs (each with its own L2).  Renumber so that they share one.
+__device__ __forceinline__ void xcd_order(int& qt, int& kvh, int& b) {
+  qt = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
+  const int nx = gridDim.x, ng = gridDim.y * gridDim.z;
+  const int lin = blockIdx.x + nx * (blockIdx.y + gridDim.y * blockIdx.z);
+  if (ng % 8 == 0) {
+    const int xcd = lin & 7, slot = lin >> 3;            // slot-th workgroup of this XCD
+    const int grp = (slot / nx) * 8 + xcd;
+    qt = slot % nx;
+    kvh = grp % gridDim.y;
+    b = grp / gridDim.y;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Prefill v3: each wave owns NT column tiles (NT x 16/G query rows x G heads) and walks the
 // KV chunks with the decode kernel's depth-2 pipeline (chunk c+1's K/V loads in flight while
@@ -525,22 +562,7 @@ __global__ void __launch_bounds__(256, NT == 1 ? 2 : 1) attn_prefill2_kernel(
     if (j < n) compute(cur, cb + j);
   }
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    float lt = st[t].lsum;
-    lt = rows_sum(lt);
-    const int crow = row0 + t * R + r / G, ch = r % G;
-    if (crow < ql) {
-      const float inv = lt > 0.f ? 1.f / lt : 0.f;
-      bf16* orow = out + ((size_t)(qs + crow) * hq + kvh * G + ch) * D;
-#pragma unroll
-      for (int dt = 0; dt < D / 16; ++dt) {
-        bf16x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = f2bf(st[t].acc[dt][i] * inv);
-        *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * g) = o;
-      }
-    }
-  }
+  for (int t = 0; t < NT; ++t) store_tile_direct<D, G>(out, st[t], row0 + t * R, qs, ql, hq, kvh, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -580,21 +602,8 @@ __global__ void __launch_bounds__(WV * 64, NT >= 4 || WV > 4 ? 1 : 2) attn_prefi
   __shared__ __attribute__((aligned(16))) bf16 smem[NB * CH + 2 * kPfMaxChunks];
   int* ids = reinterpret_cast<int*>(smem + NB * CH);
 
-  // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs in dispatch order, so the
-  // gridDim.x row tiles of one (sequence, kv head) -- which stream the same K / V chunks -- would
-  // land on gridDim.x different XCDs (each with its own L2).  Renumber so that they share one.
-  int qt = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
-  {
-    const int nx = gridDim.x, ng = gridDim.y * gridDim.z;
-    const int lin = blockIdx.x + nx * (blockIdx.y + gridDim.y * blockIdx.z);
-    if (ng % 8 == 0) {
-      const int xcd = lin & 7, slot = lin >> 3;            // slot-th workgroup of this XCD
-      const int grp = (slot / nx) * 8 + xcd;
-      qt = slot % nx;
-      kvh = grp % gridDim.y;
-      b = grp / gridDim.y;
-    }
-  }
+  int qt, kvh, b;
+  xcd_order(qt, kvh, b);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int qs = cu_seqlens_q[b], ql = cu_seqlens_q[b + 1] - qs;
@@ -644,7 +653,7 @@ __global__ void __launch_bounds__(WV * 64, NT >= 4 || WV > 4 ? 1 : 2) attn_prefi
       if (!ok) v = bf16x8{};
       qf[t][ks] = v;
     }
-    if (cos_sin != nullptr) rope_rotate<D, true>(qf[t], cos_sin + (size_t)positions[tok] * D, g);
+    if (cos_sin != nullptr) rope_rotate<D / 32, 32>(qf[t], cos_sin + (size_t)positions[tok] * D + 8 * g);
     init_state(st[t]);
   }
   const int wg_kmax = qpos0 + min(wg_row0 + WV * R * NT, ql) - 1;
@@ -731,22 +740,7 @@ __global__ void __launch_bounds__(WV * 64, NT >= 4 || WV > 4 ? 1 : 2) attn_prefi
   if constexpr (WV * NT * 16 * OLD > NB * CH) {     // (4 tiles per wave at D = 64: direct stores)
     if (!active) return;
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      float lt = st[t].lsum;
-      lt = rows_sum(lt);
-      const int crow = row0 + t * R + r / G, ch = r % G;
-      if (crow < ql) {
-        const float inv = lt > 0.f ? 1.f / lt : 0.f;
-        bf16* orow = out + ((size_t)(qs + crow) * hq + kvh * G + ch) * D;
-#pragma unroll
-        for (int dt = 0; dt < D / 16; ++dt) {
-          bf16x4 o;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) o[i] = f2bf(st[t].acc[dt][i] * inv);
-          *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * g) = o;
-        }
-      }
-    }
+    for (int t = 0; t < NT; ++t) store_tile_direct<D, G>(out, st[t], row0 + t * R, qs, ql, hq, kvh, lane);
     return;
   }
   __syncthreads();
@@ -783,7 +777,7 @@ __global__ void __launch_bounds__(WV * 64, NT >= 4 || WV > 4 ? 1 : 2) attn_prefi
 }
 
 // ---------------------------------------------------------------------------
-// Prefill v6: v4's LDS-shared K / V stream on the 32x32x16 MFMA (v_mfma_f32_32x32x16_bf16).
+// Prefill v7 and v9: v4's LDS-shared K / V stream on the 32x32x16 MFMA (v_mfma_f32_32x32x16_bf16).
 // S^T = K Q^T per 64-key tile (two 32-key blocks): a lane holds 32 scores of ONE column (query row
 // x head) -- 16 per block, rows 8 j + 4 hi + i of the 32x32 result -- so the column max is in-lane
 // plus one v_permlane32_swap, and the per-column softmax work (max, alpha, denominator update,
@@ -795,11 +789,18 @@ __global__ void __launch_bounds__(WV * 64, NT >= 4 || WV > 4 ? 1 : 2) attn_prefi
 // P.V B operand of MFMA (bb, h) is the bf16 conversion of 8 consecutive score registers (P never
 // leaves the lane), and its V^T A operand is one 16-byte read of key group 2 h + hi of the cache's
 // [4][D][8] V^T block.  Workgroup: 8 waves x 32 columns (32 / G query rows x G heads each) of one
-// (sequence, kv head); K / V tiles stream through a 3-deep LDS ring by LDS-DMA with v4's XOR-swizzled
+// (sequence, kv head); K / V tiles stream through a 4-deep LDS ring by LDS-DMA with v4's XOR-swizzled
 // K rows, conflict-free for this read pattern as well (the 16 lanes of a ds_read_b128 group hit 16
-// distinct row & 15 values).
+// distinct row & 15 values).  The tile code below is shared by v7 (one workgroup per row tile) and v9
+// (persistent).  (v6, this kernel without the P.V / softmax overlap and a 3-deep ring, was slower than
+// v7 at every measured shape and is removed: profiles/round6_attention.md.)
 // ---------------------------------------------------------------------------
 constexpr int kW32Waves = 8;
+constexpr int kW32D = 128;                        // head_dim
+constexpr int kW32TK = 2 * kBS;                   // keys per tile
+constexpr int kW32Blk = kBS * kW32D;              // bf16 elements of one K block (= one V^T block)
+constexpr int kW32Tile = 4 * kW32Blk;             // K0 K1 V0 V1: 32 KiB
+constexpr int kW32NB = 4;                         // ring depth: a tile's V^T is still read one iteration after its K
 
 // physical K row (common.h krow32 layout) of the key pi(m) the QK^T A operand puts at MFMA row m
 __device__ __forceinline__ int w32_krow(int m) {
@@ -816,41 +817,176 @@ __device__ __forceinline__ float half_sum(float v) {
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 
-template <int G, bool PIPE>
+// Q^T fragments (B operand) of this lane's column m -- head kvh * G + m % G of token row tok of q, row
+// stride q_stride -- dims 16 ks + 8 hi + 0..7; RoPE partners (d, d + 64) are fragments ks and ks + 4 of
+// the same lane, rotated in registers when cos_sin is given.  !ok (a column past the sequence): zeros.
+template <int G>
+__device__ __forceinline__ void w32_load_q(bf16x8 (&qf)[kW32D / 16], const bf16* __restrict__ q, int q_stride,
+                                           int tok, int kvh, const int32_t* __restrict__ positions,
+                                           const float* __restrict__ cos_sin, bool ok, int m, int hi) {
+  const bf16* qrow = q + (size_t)tok * q_stride + (size_t)(kvh * G + m % G) * kW32D + 8 * hi;
+#pragma unroll
+  for (int ks = 0; ks < kW32D / 16; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + 16 * ks);
+  if (cos_sin != nullptr)
+    rope_rotate<kW32D / 16, 16>(qf, cos_sin + (size_t)positions[tok] * kW32D + 8 * hi);
+  if (!ok) {
+#pragma unroll
+    for (int ks = 0; ks < kW32D / 16; ++ks) qf[ks] = bf16x8{};
+  }
+}
+
+// Staging one tile by LDS-DMA is NOT among these helpers: each kernel keeps its own `stage` lambda.  As a
+// shared function hipcc merged v9's staging call sites (this item's / the next item's tile: 28 LDS-DMA
+// instructions where the lambdas give 40, the block id behind a select) and v9 ran 2-5 % slower from
+// 1k-token prompts up (profiles/attention_refactor.md).
+constexpr int kW32GL = kW32Tile / 512 / kW32Waves;   // 1 KiB LDS-DMA pieces per wave per tile
+static_assert(kW32GL == 4 && kW32GL * 2 == 8, "tile pieces: one part per wave");
+
+// S^T of the tile in ring slot tb (two blocks): 16 MFMAs reading K fragments from the ring.
+// krow = w32_krow(m), the lane's physical K row.
+__device__ __forceinline__ void w32_qk(f32x16& s0, f32x16& s1, const bf16* tb, const bf16x8 (&qf)[kW32D / 16],
+                                       int krow, int hi) {
+  const int kswz = krow & 15;
+  s0 = f32x16{};
+  s1 = f32x16{};
+#pragma unroll
+  for (int ks = 0; ks < kW32D / 16; ++ks) {
+    const int slot = ((2 * ks + hi) ^ kswz) * 8;
+    const bf16x8 ka = *reinterpret_cast<const bf16x8*>(tb + krow * kW32D + slot);
+    const bf16x8 kb = *reinterpret_cast<const bf16x8*>(tb + kW32Blk + krow * kW32D + slot);
+    s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[ks], s0, 0, 0, 0);
+    s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb, qf[ks], s1, 0, 0, 0);
+  }
+}
+
+// causal mask: register r of block bb holds key k0 + 32 bb + 16 (r >> 3) + 8 hi + (r & 7).  Called behind
+// a wave-uniform branch in ONE instantiation of the tile: two (masked / unmasked) copies of the tile made
+// hipcc keep the accumulators in different registers per copy and shuffle all 64 (v_mov_b64 x 32) at merges
+__device__ __forceinline__ void w32_mask(f32x16& s0, f32x16& s1, int kmax_col, int k0, int hi) {
+  const int kl = kmax_col - k0 - 8 * hi;           // admissible: 16 (r >> 3) + (r & 7) (+ 32) <= kl
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int key = 16 * (r >> 3) + (r & 7);
+    s0[r] = key <= kl ? s0[r] : -INFINITY;
+    s1[r] = key + kBS <= kl ? s1[r] : -INFINITY;
+  }
+}
+
+// V^T fragment (P.V A operand) of the tile in ring slot vt: d-tile dt, P operand bh (block bh >> 1,
+// key group 2 (bh & 1) + hi)
+__device__ __forceinline__ bf16x8 w32_vfrag(const bf16* vt, int dt, int bh, int m, int hi) {
+  return *reinterpret_cast<const bf16x8*>(vt + 2 * kW32Blk + (bh >> 1) * kW32Blk +
+                                          ((2 * (bh & 1) + hi) * kW32D + 32 * dt + m) * 8);
+}
+
+// Online softmax of this tile's scores (s0, s1) under the PREVIOUS tile's P.V (its probabilities pbp,
+// its V^T in ring slot vt): the P.V MFMAs go out right behind this tile's QK^T and run while the VALU
+// does this tile's softmax (MFMA and VALU are separate pipes; without it a wave's P.V waits for its own
+// softmax, and only the other wave on the SIMD can fill the gap).  That is why the ring is one deeper
+// than v4's, and why an active wave runs every tile of the workgroup (past its own rows' keys the scores
+// are all masked: P = 0, alpha = 1): the accumulators see one straight-line path per iteration -- a skip
+// path made hipcc copy all 64 of them in and out of the tile code.  pbp starts as zeros (a no-op P.V) and
+// leaves as this tile's P; the last tile's P.V is w32_pv_tail.
+// The 16 P.V MFMAs carry the softmax in their gaps, one slice per gap (sched_barrier(0) fences each gap):
+// gaps 0-3 the column max over registers 4 k .. 4 k + 3 of both blocks, gap 4 the cross-half max and the
+// running-max update, gaps 5-15 the 16 score pairs (FMA, two exp, cvt, sum).  MFMA i: d-tile i & 3
+// (consecutive MFMAs on different accumulators), P operand i >> 2; its V^T fragment is read one group of
+// four ahead.
+__device__ __forceinline__ void w32_softmax_under_pv(f32x16 (&acc)[kW32D / 32], const f32x16& s0, const f32x16& s1,
+                                                     bf16x8 (&pbp)[4], const bf16* vt, float& mrun, float& lsum,
+                                                     float scale_log2, int m, int hi) {
+  const f32x2 sc2 = {scale_log2, scale_log2};
+  auto vread = [&](int i) { return w32_vfrag(vt, i & 3, i >> 2, m, hi); };
+  bf16x8 va[4], vn[4], pb[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) va[j] = vread(j);
+  float cmp[4], alpha = 1.f, mref = 0.f;
+  f32x2 sum2 = {0.f, 0.f};
+  auto pair = [&](int p) {                         // score pair p: block p / 8, registers 2 (p % 8) + 0, 1
+    const f32x16& sv = p < 8 ? s0 : s1;
+    const int r = 2 * (p & 7);
+    const f32x2 x = __builtin_elementwise_fma(f32x2{sv[r], sv[r + 1]}, sc2, f32x2{-mref, -mref});
+    const f32x2 e = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
+    sum2 += e;
+    pb[p >> 2][r & 7] = f2bf(e[0]);
+    pb[p >> 2][(r & 7) + 1] = f2bf(e[1]);
+  };
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    if ((i & 3) == 0 && i + 4 < 16) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) vn[j] = vread(i + 4 + j);
+    }
+    acc[i & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va[i & 3], pbp[i >> 2], acc[i & 3], 0, 0, 0);
+    if ((i & 3) == 3 && i + 1 < 16) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) va[j] = vn[j];
+    }
+    if (i < 4) {
+      cmp[i] = fmaxf(fmaxf(fmaxf(s0[4 * i], s0[4 * i + 1]), fmaxf(s0[4 * i + 2], s0[4 * i + 3])),
+                     fmaxf(fmaxf(s1[4 * i], s1[4 * i + 1]), fmaxf(s1[4 * i + 2], s1[4 * i + 3])));
+    } else if (i == 4) {
+      const float cm = half_max(fmaxf(fmaxf(cmp[0], cmp[1]), fmaxf(cmp[2], cmp[3]))) * scale_log2;
+      const float mn = fmaxf(mrun, cm);
+      mref = (mn == -INFINITY) ? 0.f : mn;
+      alpha = __builtin_amdgcn_exp2f(mrun - mref);
+      mrun = mn;
+    } else if (i < 10) {
+      pair(2 * (i - 5));
+      pair(2 * (i - 5) + 1);
+    } else {
+      pair(i);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // pin the probabilities and their sum here: hipcc would otherwise sink the exp / cvt / add work
+  // past the rescale branch below, out of the MFMAs' shadow
+#pragma unroll
+  for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(pb[i]));
+  asm volatile("" : "+v"(sum2));
+  lsum = lsum * alpha + (sum2[0] + sum2[1]);
+  if (__any(alpha != 1.f)) {                        // exactly 1 wherever no column's max moved
+#pragma unroll
+    for (int dt = 0; dt < kW32D / 32; ++dt) acc[dt] *= alpha;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) pbp[i] = pb[i];
+}
+
+// the last tile's P.V: O^T += V^T P^T for the tile in ring slot vt, 16 MFMAs reading V^T from the ring
+__device__ __forceinline__ void w32_pv_tail(f32x16 (&acc)[kW32D / 32], const bf16x8 (&pbp)[4], const bf16* vt,
+                                            int m, int hi) {
+#pragma unroll
+  for (int dt = 0; dt < kW32D / 32; ++dt) {
+#pragma unroll
+    for (int bh = 0; bh < 4; ++bh)
+      acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w32_vfrag(vt, dt, bh, m, hi), pbp[bh], acc[dt], 0, 0, 0);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Prefill v7: one workgroup per row tile of a (sequence, kv head); prologue, one-shot ring loop over the
+// workgroup's tiles, output through an LDS image.
+// ---------------------------------------------------------------------------
+template <int G>
 __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32_kernel(
     bf16* __restrict__ out, const bf16* __restrict__ q, const bf16* __restrict__ k_cache,
     const bf16* __restrict__ v_cache, const int32_t* __restrict__ block_tables,
     const int32_t* __restrict__ cu_seqlens_q, const int32_t* __restrict__ seq_lens, int hq, int hkv,
     int max_blocks, float scale_log2, const int32_t* __restrict__ positions, const float* __restrict__ cos_sin,
     int q_stride) {
-  constexpr int D = 128;
-  constexpr int WV = kW32Waves;
+  constexpr int D = kW32D, WV = kW32Waves, TK = kW32TK, BLK = kW32Blk, TILE = kW32Tile, NB = kW32NB;
   constexpr int R = 32 / G;                       // query rows per wave
-  constexpr int TK = 2 * kBS;                     // keys per tile
-  constexpr int BLK = kBS * D;                    // bf16 elements of one K block (= one V^T block)
-  constexpr int TILE = 4 * BLK;                   // K0 K1 V0 V1: 32 KiB
-  constexpr int NB = PIPE ? 4 : 3;                // ring depth
-  constexpr int GL = TILE / 512 / WV;             // 1 KiB LDS-DMA pieces per wave per tile
-  static_assert(GL == 4 && 32 % G == 0, "tile pieces / column tiling");
+  static_assert(32 % G == 0, "column tiling");
   __shared__ __attribute__((aligned(16))) bf16 smem[NB * TILE + 2 * kPfMaxChunks];
   int* ids = reinterpret_cast<int*>(smem + NB * TILE);
 
   // XCD-aware order (as v4): the row tiles of one (sequence, kv head) share an XCD's L2; and the
   // last row tiles -- the most keys under the causal mask -- are dispatched first, so the long
   // workgroups do not form the launch's tail
-  int qt = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
-  {
-    const int nx = gridDim.x, ng = gridDim.y * gridDim.z;
-    const int lin = blockIdx.x + nx * (blockIdx.y + gridDim.y * blockIdx.z);
-    if (ng % 8 == 0) {
-      const int xcd = lin & 7, slot = lin >> 3;
-      const int grp = (slot / nx) * 8 + xcd;
-      qt = slot % nx;
-      kvh = grp % gridDim.y;
-      b = grp / gridDim.y;
-    }
-    qt = nx - 1 - qt;
-  }
+  int qt, kvh, b;
+  xcd_order(qt, kvh, b);
+  qt = gridDim.x - 1 - qt;
   // the wave index through readfirstlane: hipcc then knows it (and every bound derived from it) is
   // wave-uniform and branches on it with scalar branches instead of EXEC masks
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -863,43 +999,14 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32_kernel(
   const int ctx = seq_lens[b];
   const int qpos0 = ctx - ql;
   // this lane's column: query row row0 + m / G, head kvh * G + m % G
-  const int crow = row0 + m / G, ch = m % G;
+  const int crow = row0 + m / G;
   const bool ok = crow < ql;
   const int kmax_col = ok ? qpos0 + crow : -1;
-  const int tok = qs + (ok ? crow : 0);
-  // Q^T fragments (B operand): column m, dims 16 ks + 8 hi + 0..7; RoPE partners (d, d + 64) are
-  // fragments ks and ks + 4 of the same lane
   bf16x8 qf[D / 16];
-  {
-    const bf16* qrow = q + (size_t)tok * q_stride + (size_t)(kvh * G + ch) * D + 8 * hi;
-#pragma unroll
-    for (int ks = 0; ks < D / 16; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + 16 * ks);
-    if (cos_sin != nullptr) {
-      const float* cs = cos_sin + (size_t)positions[tok] * D + 8 * hi;
-#pragma unroll
-      for (int ks = 0; ks < D / 32; ++ks) {
-        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cs + 16 * ks);
-        const f32x4 c1 = *reinterpret_cast<const f32x4*>(cs + 16 * ks + 4);
-        const f32x4 s0 = *reinterpret_cast<const f32x4*>(cs + D / 2 + 16 * ks);
-        const f32x4 s1 = *reinterpret_cast<const f32x4*>(cs + D / 2 + 16 * ks + 4);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float c = j < 4 ? c0[j] : c1[j - 4], s = j < 4 ? s0[j] : s1[j - 4];
-          const float a = bf2f(qf[ks][j]), bq = bf2f(qf[ks + D / 32][j]);
-          qf[ks][j] = f2bf(__builtin_fmaf(a, c, -(bq * s)));   // as rope_rotate: explicit FMAs
-          qf[ks + D / 32][j] = f2bf(__builtin_fmaf(bq, c, a * s));
-        }
-      }
-    }
-    if (!ok) {
-#pragma unroll
-      for (int ks = 0; ks < D / 16; ++ks) qf[ks] = bf16x8{};
-    }
-  }
+  w32_load_q<G>(qf, q, q_stride, qs + (ok ? crow : 0), kvh, positions, cos_sin, ok, m, hi);
   const int wg_kmax = qpos0 + min(wg_row0 + WV * R, ql) - 1;
   const int nch = wg_kmax / kBS + 1;              // 32-key blocks the workgroup reads
   const int ntile = (nch + 1) / 2;
-  const int wave_kmax = active ? qpos0 + min(row0 + R, ql) - 1 : -1;
   const int wave_kmin = row0 + R <= ql ? qpos0 + row0 : -1;   // -1: a column past the sequence
   const int32_t* bt = block_tables + (size_t)b * max_blocks;
   for (int i = threadIdx.x; i < nch; i += WV * 64) ids[i] = bt[i];
@@ -911,17 +1018,16 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32_kernel(
   const size_t head_off = (size_t)kvh * BLK;
   const size_t blk_stride = (size_t)hkv * BLK;
   // wave w stages 1 KiB pieces 4 w .. 4 w + 3 of tile t: pieces 0-7 K block 0, 8-15 K block 1,
-  // 16-23 V^T block 0, 24-31 V^T block 1 (a block past the sequence re-reads the last one: its keys
-  // are masked for every column)
+  // 16-23 V^T block 0, 24-31 V^T block 1 (a block past the sequence re-reads the last one: its keys are
+  // masked for every column)
   // (a wave's four pieces are one part: one block id per wave, read once and made scalar)
   auto stage = [&](int t, int buf) {
     bf16* dst = smem + buf * TILE;
-    static_assert(GL * 2 == 8, "one part per wave");
     const int c = min(2 * t + ((w >> 1) & 1), nch - 1);
     const size_t base = (size_t)__builtin_amdgcn_readfirstlane(ids[c]) * blk_stride + head_off;
 #pragma unroll
-    for (int j = 0; j < GL; ++j) {
-      const int i = w * GL + j, part = i >> 3;
+    for (int j = 0; j < kW32GL; ++j) {
+      const int i = w * kW32GL + j, part = i >> 3;
       const bf16* src;
       if (part < 2) {
         const int rr = (i & 7) * 4 + lane / 16, cs = lane % 16;
@@ -932,190 +1038,38 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32_kernel(
       __builtin_amdgcn_global_load_lds((glb_vptr_a)src, (lds_vptr_a)(dst + i * 512), 16, 0, 0);
     }
   };
-  const int krow = w32_krow(m), kswz = krow & 15;
+  const int krow = w32_krow(m);
   f32x16 acc[D / 32];                             // O^T: dims 32 dt + 8 (r / 4) + 4 hi + r % 4, column m
 #pragma unroll
   for (int dt = 0; dt < D / 32; ++dt) acc[dt] = f32x16{};
   float mrun = -INFINITY, lsum = 0.f;
-  const f32x2 sc2 = {scale_log2, scale_log2};
-
-  // S^T of tile tb (two blocks): 16 MFMAs reading K fragments from the ring
-  auto qk = [&](const bf16* tb, f32x16& s0, f32x16& s1) {
-    s0 = f32x16{};
-    s1 = f32x16{};
-#pragma unroll
-    for (int ks = 0; ks < D / 16; ++ks) {
-      const int slot = ((2 * ks + hi) ^ kswz) * 8;
-      const bf16x8 ka = *reinterpret_cast<const bf16x8*>(tb + krow * D + slot);
-      const bf16x8 kb = *reinterpret_cast<const bf16x8*>(tb + BLK + krow * D + slot);
-      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[ks], s0, 0, 0, 0);
-      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb, qf[ks], s1, 0, 0, 0);
-    }
-  };
-  // causal mask: register r of block bb holds key k0 + 32 bb + 16 (r >> 3) + 8 hi + (r & 7).  Behind a
-  // wave-uniform branch in ONE instantiation: two (masked / unmasked) copies of the tile made hipcc
-  // keep the accumulators in different registers per copy and shuffle all 64 (v_mov_b64 x 32) at merges
-  auto mask = [&](f32x16& s0, f32x16& s1, int k0) {
-    const int kl = kmax_col - k0 - 8 * hi;         // admissible: 16 (r >> 3) + (r & 7) (+ 32) <= kl
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = 16 * (r >> 3) + (r & 7);
-      s0[r] = key <= kl ? s0[r] : -INFINITY;
-      s1[r] = key + kBS <= kl ? s1[r] : -INFINITY;
-    }
-  };
-  // online softmax of one tile's scores: the P.V B operands pb[2 bb + h], the rescale factor
-  auto softmax = [&](const f32x16& s0, const f32x16& s1, bf16x8 (&pb)[4]) {
-    float cm = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cm = fmaxf(cm, fmaxf(s0[r], s1[r]));
-    cm = half_max(cm) * scale_log2;
-    const float mn = fmaxf(mrun, cm);
-    const float mref = (mn == -INFINITY) ? 0.f : mn;
-    const float alpha = __builtin_amdgcn_exp2f(mrun - mref);
-    mrun = mn;
-    const f32x2 mr2 = {-mref, -mref};
-    f32x2 sum2 = {0.f, 0.f};
-#pragma unroll
-    for (int p = 0; p < 16; ++p) {                 // score pairs: block p / 8, registers 2 (p % 8) + 0, 1
-      const f32x16& sv = p < 8 ? s0 : s1;
-      const int r = 2 * (p & 7);
-      const f32x2 x = __builtin_elementwise_fma(f32x2{sv[r], sv[r + 1]}, sc2, mr2);
-      const f32x2 e = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
-      sum2 += e;
-      pb[p >> 2][r & 7] = f2bf(e[0]);
-      pb[p >> 2][(r & 7) + 1] = f2bf(e[1]);
-    }
-    lsum = lsum * alpha + (sum2[0] + sum2[1]);
-    return alpha;
-  };
-  auto rescale = [&](float alpha) {
-    if (__any(alpha != 1.f)) {                      // exactly 1 wherever no column's max moved
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt) acc[dt] *= alpha;
-    }
-  };
-  // O^T += V^T P^T for the tile in ring slot tb: 16 MFMAs reading V^T fragments from the ring
-  auto pv = [&](const bf16* tb, const bf16x8 (&pb)[4]) {
-#pragma unroll
-    for (int dt = 0; dt < D / 32; ++dt) {
-#pragma unroll
-      for (int bh = 0; bh < 4; ++bh) {
-        const bf16x8 va = *reinterpret_cast<const bf16x8*>(
-            tb + 2 * BLK + (bh >> 1) * BLK + ((2 * (bh & 1) + hi) * D + 32 * dt + m) * 8);
-        acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pb[bh], acc[dt], 0, 0, 0);
-      }
-    }
-  };
 
   stage(0, 0);
   if (ntile > 1) stage(1, 1);
-  // PIPE: the previous tile's P.V MFMAs go out right behind this tile's QK^T and run while the VALU
-  // does this tile's softmax (MFMA and VALU are separate pipes; without it a wave's P.V waits for
-  // its own softmax, and only the other wave on the SIMD can fill the gap).  The ring is one deeper:
-  // a tile's V^T is still read one iteration after its K.  An active wave runs every tile of the
-  // workgroup (past its own rows' keys the scores are all masked: P = 0, alpha = 1) so that the
-  // accumulators see one straight-line path per iteration -- a skip path made hipcc copy all 64 of
-  // them in and out of the tile code
-  bf16x8 pbp[4] = {};                             // PIPE: P of the previous tile (zeros: a no-op P.V)
-  int vprev = 0;                                  // PIPE: its ring slot
+  bf16x8 pbp[4] = {};                             // P of the previous tile (zeros: a no-op P.V)
+  int vprev = 0;                                  // its ring slot
   for (int t = 0; t < ntile; ++t) {
     if (t + 1 < ntile) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    // slot (t + 2) % NB was last read in iteration t - 1 (PIPE: t - 2's V^T in iteration t - 1), which
-    // every wave finished before the barrier
-    const bf16* tb = smem + (t % NB) * TILE;
-    const int k0 = t * TK;
-    if constexpr (PIPE) {
-      // PIPE stages behind this tile's QK^T: the block-id read and address work then run under the
-      // MFMAs instead of between the barrier and the first of them
-      if (!active) {
-        if (t + 2 < ntile) stage(t + 2, (t + 2) % NB);
-        continue;
-      }
-      f32x16 s0, s1;
-      qk(tb, s0, s1);
-      __builtin_amdgcn_sched_barrier(0);
+    // slot (t + 2) % NB was last read in iteration t - 1 (t - 2's V^T), which every wave finished
+    // before the barrier.  Active waves stage it behind this tile's QK^T: the block-id read and address
+    // work then run under the MFMAs instead of between the barrier and the first of them
+    if (!active) {
       if (t + 2 < ntile) stage(t + 2, (t + 2) % NB);
-      if (k0 + TK - 1 > wave_kmin) mask(s0, s1, k0);   // unmasked below every column's diagonal
-      // the previous tile's 16 P.V MFMAs with this tile's softmax in their gaps, one slice per gap
-      // (sched_barrier(0) fences each gap): gaps 0-3 the column max over registers 4 k .. 4 k + 3 of
-      // both blocks, gap 4 the cross-half max and the running-max update, gaps 5-15 the 16 score pairs
-      // (FMA, two exp, cvt, sum).  MFMA i: d-tile i & 3 (consecutive MFMAs on different accumulators),
-      // P operand i >> 2; its V^T fragment is read one group of four ahead.
-      const bf16* vt = smem + vprev * TILE;
-      auto vread = [&](int i) {
-        const int dt = i & 3, bh = i >> 2;
-        return *reinterpret_cast<const bf16x8*>(vt + 2 * BLK + (bh >> 1) * BLK +
-                                                ((2 * (bh & 1) + hi) * D + 32 * dt + m) * 8);
-      };
-      bf16x8 va[4], vn[4], pb[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) va[j] = vread(j);
-      float cmp[4], alpha = 1.f, mref = 0.f;
-      f32x2 sum2 = {0.f, 0.f};
-      auto pair = [&](int p) {                     // score pair p: block p / 8, registers 2 (p % 8) + 0, 1
-        const f32x16& sv = p < 8 ? s0 : s1;
-        const int r = 2 * (p & 7);
-        const f32x2 x = __builtin_elementwise_fma(f32x2{sv[r], sv[r + 1]}, sc2, f32x2{-mref, -mref});
-        const f32x2 e = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
-        sum2 += e;
-        pb[p >> 2][r & 7] = f2bf(e[0]);
-        pb[p >> 2][(r & 7) + 1] = f2bf(e[1]);
-      };
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        if ((i & 3) == 0 && i + 4 < 16) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) vn[j] = vread(i + 4 + j);
-        }
-        acc[i & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va[i & 3], pbp[i >> 2], acc[i & 3], 0, 0, 0);
-        if ((i & 3) == 3 && i + 1 < 16) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) va[j] = vn[j];
-        }
-        if (i < 4) {
-          cmp[i] = fmaxf(fmaxf(fmaxf(s0[4 * i], s0[4 * i + 1]), fmaxf(s0[4 * i + 2], s0[4 * i + 3])),
-                         fmaxf(fmaxf(s1[4 * i], s1[4 * i + 1]), fmaxf(s1[4 * i + 2], s1[4 * i + 3])));
-        } else if (i == 4) {
-          const float cm = half_max(fmaxf(fmaxf(cmp[0], cmp[1]), fmaxf(cmp[2], cmp[3]))) * scale_log2;
-          const float mn = fmaxf(mrun, cm);
-          mref = (mn == -INFINITY) ? 0.f : mn;
-          alpha = __builtin_amdgcn_exp2f(mrun - mref);
-          mrun = mn;
-        } else if (i < 10) {
-          pair(2 * (i - 5));
-          pair(2 * (i - 5) + 1);
-        } else {
-          pair(i);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      // pin the probabilities and their sum here: hipcc would otherwise sink the exp / cvt / add work
-      // past the rescale branch below, out of the MFMAs' shadow
-#pragma unroll
-      for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(pb[i]));
-      asm volatile("" : "+v"(sum2));
-      lsum = lsum * alpha + (sum2[0] + sum2[1]);
-      rescale(alpha);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) pbp[i] = pb[i];
-      vprev = t % NB;
-    } else if (t + 2 < ntile) {
-      stage(t + 2, (t + 2) % NB);
+      continue;
     }
-    if (!PIPE && k0 <= wave_kmax) {
-      f32x16 s0, s1;
-      qk(tb, s0, s1);
-      if (k0 + TK - 1 > wave_kmin) mask(s0, s1, k0);
-      bf16x8 pb[4];
-      rescale(softmax(s0, s1, pb));
-      pv(tb, pb);
-    }
+    const int k0 = t * TK;
+    f32x16 s0, s1;
+    w32_qk(s0, s1, smem + (t % NB) * TILE, qf, krow, hi);
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 2 < ntile) stage(t + 2, (t + 2) % NB);
+    if (k0 + TK - 1 > wave_kmin) w32_mask(s0, s1, kmax_col, k0, hi);   // unmasked below every column's diagonal
+    w32_softmax_under_pv(acc, s0, s1, pbp, smem + vprev * TILE, mrun, lsum, scale_log2, m, hi);
+    vprev = t % NB;
   }
-  if (PIPE && active) pv(smem + vprev * TILE, pbp);
+  if (active) w32_pv_tail(acc, pbp, smem + vprev * TILE, m, hi);
   const float lt = half_sum(lsum);
   // output through a wave-private LDS image (the ring is free once every wave is past its last
   // tile): whole 16-byte pieces of a column per store, G heads of a row contiguous -- whole lines
@@ -1155,7 +1109,7 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32_kernel(
 // snake over heavy-first order (round r of the XCD's PX workgroups runs left to right, r + 1 right to
 // left: a workgroup's heavy and light row tiles pair up).  The LDS ring runs on a global tile count
 // across items: the next item's first two K / V tiles are staged under the current item's last two
-// (their block ids straight from the table), so an item starts on landed data; its q loads and the
+// (their block ids from the second LDS list), so an item starts on landed data; its q loads and the
 // previous item's output stores are the only latency left at a switch.  Output goes straight from
 // the accumulators (the ring is busy): the two half-waves swap dword pairs with v_permlane32_swap so
 // that every lane stores 16 contiguous bytes of its column.
@@ -1167,16 +1121,10 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32p_kernel(
     const int32_t* __restrict__ cu_seqlens_q, const int32_t* __restrict__ seq_lens, int hq, int hkv,
     int max_blocks, float scale_log2, const int32_t* __restrict__ positions, const float* __restrict__ cos_sin,
     int q_stride, int nx, int ngroups) {
-  constexpr int D = 128;
-  constexpr int WV = kW32Waves;
+  constexpr int D = kW32D, WV = kW32Waves, TK = kW32TK, BLK = kW32Blk, TILE = kW32Tile, NB = kW32NB;
   constexpr int R = 32 / G;                       // query rows per wave
   constexpr int RWG = WV * R;                     // query rows per item
-  constexpr int TK = 2 * kBS;
-  constexpr int BLK = kBS * D;
-  constexpr int TILE = 4 * BLK;
-  constexpr int NB = 4;
-  constexpr int GL = TILE / 512 / WV;
-  static_assert(GL == 4 && 32 % G == 0, "tile pieces / column tiling");
+  static_assert(32 % G == 0, "column tiling");
   __shared__ __attribute__((aligned(16))) bf16 smem[NB * TILE + 4 * kPfMaxChunks];
   int* ids = reinterpret_cast<int*>(smem + NB * TILE);   // two block-id lists: this item's, the next's
 
@@ -1223,6 +1171,7 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32p_kernel(
   // LDS: the next item's list is written in this item's prologue, so its first tiles can be staged
   // under this item's last ones.  (Reading them from the table for the first tiles instead made a
   // select between a global and an LDS pointer, a flat load, whose wait drains the DMA just issued.)
+  // (pieces and block choice as v7's stage)
   auto stage = [&](const Item& it, int il, int t, int buf) {
     bf16* dst = smem + buf * TILE;
     const size_t head_off = (size_t)it.kvh * BLK;
@@ -1230,8 +1179,8 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32p_kernel(
     const int id = __builtin_amdgcn_readfirstlane(ids[il * kPfMaxChunks + c]);
     const size_t base = (size_t)id * blk_stride + head_off;
 #pragma unroll
-    for (int j = 0; j < GL; ++j) {
-      const int i = w * GL + j, part = i >> 3;
+    for (int j = 0; j < kW32GL; ++j) {
+      const int i = w * kW32GL + j, part = i >> 3;
       const bf16* src;
       if (part < 2) {
         const int rr = (i & 7) * 4 + lane / 16, cs = lane % 16;
@@ -1265,8 +1214,7 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32p_kernel(
   stage_global(0, false);
   stage_global(1, false);
 
-  const int krow = w32_krow(m), kswz = krow & 15;
-  const f32x2 sc2 = {scale_log2, scale_log2};
+  const int krow = w32_krow(m);
   while (true) {
     // ---- item prologue: this lane's column, q (rotated), LDS block ids of tiles >= 2
     const int row0 = cur.row0 + w * R;
@@ -1274,36 +1222,10 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32p_kernel(
     const int crow = row0 + m / G, ch = m % G;
     const bool ok = crow < cur.ql;
     const int kmax_col = ok ? cur.qpos0 + crow : -1;
-    const int tok = cur.qs + (ok ? crow : 0);
     const int wave_kmin = row0 + R <= cur.ql ? cur.qpos0 + row0 : -1;
     bf16x8 qf[D / 16];
-    {
-      const bf16* qrow = q + (size_t)tok * q_stride + (size_t)(cur.kvh * G + ch) * D + 8 * hi;
-#pragma unroll
-      for (int ks = 0; ks < D / 16; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + 16 * ks);
-      if (cos_sin != nullptr) {
-        const float* cs = cos_sin + (size_t)positions[tok] * D + 8 * hi;
-#pragma unroll
-        for (int ks = 0; ks < D / 32; ++ks) {
-          const f32x4 c0 = *reinterpret_cast<const f32x4*>(cs + 16 * ks);
-          const f32x4 c1 = *reinterpret_cast<const f32x4*>(cs + 16 * ks + 4);
-          const f32x4 s0 = *reinterpret_cast<const f32x4*>(cs + D / 2 + 16 * ks);
-          const f32x4 s1 = *reinterpret_cast<const f32x4*>(cs + D / 2 + 16 * ks + 4);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float c = j < 4 ? c0[j] : c1[j - 4], s = j < 4 ? s0[j] : s1[j - 4];
-            const float a = bf2f(qf[ks][j]), bq = bf2f(qf[ks + D / 32][j]);
-            qf[ks][j] = f2bf(__builtin_fmaf(a, c, -(bq * s)));
-            qf[ks + D / 32][j] = f2bf(__builtin_fmaf(bq, c, a * s));
-          }
-        }
-      }
-      if (!ok) {
-#pragma unroll
-        for (int ks = 0; ks < D / 16; ++ks) qf[ks] = bf16x8{};
-      }
-    }
-    if (rn >= 0) {                                  // the next item's block ids (its list was the
+    w32_load_q<G>(qf, q, q_stride, cur.qs + (ok ? crow : 0), cur.kvh, positions, cos_sin, ok, m, hi);
+    if (rn >= 0) {                                 // the next item's block ids (its list was the
       const int32_t* bt = block_tables + (size_t)nxt.b * max_blocks;   // previous item's: all read)
       int* dst = ids + (il ^ 1) * kPfMaxChunks;
       for (int i = threadIdx.x; i < nxt.nch; i += WV * 64) dst[i] = bt[i];
@@ -1336,101 +1258,18 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32p_kernel(
         if (staged == gidx + 2) stage_global(gidx + 2, true);
         continue;
       }
-      const bf16* tb = smem + (gidx % NB) * TILE;
       const int k0 = t * TK;
-      f32x16 s0 = {}, s1 = {};
-#pragma unroll
-      for (int ks = 0; ks < D / 16; ++ks) {
-        const int slot = ((2 * ks + hi) ^ kswz) * 8;
-        const bf16x8 ka = *reinterpret_cast<const bf16x8*>(tb + krow * D + slot);
-        const bf16x8 kb = *reinterpret_cast<const bf16x8*>(tb + BLK + krow * D + slot);
-        s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[ks], s0, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb, qf[ks], s1, 0, 0, 0);
-      }
+      f32x16 s0, s1;
+      w32_qk(s0, s1, smem + (gidx % NB) * TILE, qf, krow, hi);
       __builtin_amdgcn_sched_barrier(0);
       if (staged == gidx + 1) stage_global(gidx + 1, true);
       if (staged == gidx + 2) stage_global(gidx + 2, true);
-      if (k0 + TK - 1 > wave_kmin) {
-        const int kl = kmax_col - k0 - 8 * hi;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = 16 * (r >> 3) + (r & 7);
-          s0[r] = key <= kl ? s0[r] : -INFINITY;
-          s1[r] = key + kBS <= kl ? s1[r] : -INFINITY;
-        }
-      }
-      const bf16* vt = smem + vprev * TILE;
-      auto vread = [&](int i) {
-        const int dt = i & 3, bh = i >> 2;
-        return *reinterpret_cast<const bf16x8*>(vt + 2 * BLK + (bh >> 1) * BLK +
-                                                ((2 * (bh & 1) + hi) * D + 32 * dt + m) * 8);
-      };
-      bf16x8 va[4], vn[4], pb[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) va[j] = vread(j);
-      float cmp[4], alpha = 1.f, mref = 0.f;
-      f32x2 sum2 = {0.f, 0.f};
-      auto pair = [&](int p) {
-        const f32x16& sv = p < 8 ? s0 : s1;
-        const int r = 2 * (p & 7);
-        const f32x2 x = __builtin_elementwise_fma(f32x2{sv[r], sv[r + 1]}, sc2, f32x2{-mref, -mref});
-        const f32x2 e = {__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1])};
-        sum2 += e;
-        pb[p >> 2][r & 7] = f2bf(e[0]);
-        pb[p >> 2][(r & 7) + 1] = f2bf(e[1]);
-      };
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {                // as v7: the previous tile's P.V under this softmax
-        if ((i & 3) == 0 && i + 4 < 16) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) vn[j] = vread(i + 4 + j);
-        }
-        acc[i & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va[i & 3], pbp[i >> 2], acc[i & 3], 0, 0, 0);
-        if ((i & 3) == 3 && i + 1 < 16) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) va[j] = vn[j];
-        }
-        if (i < 4) {
-          cmp[i] = fmaxf(fmaxf(fmaxf(s0[4 * i], s0[4 * i + 1]), fmaxf(s0[4 * i + 2], s0[4 * i + 3])),
-                         fmaxf(fmaxf(s1[4 * i], s1[4 * i + 1]), fmaxf(s1[4 * i + 2], s1[4 * i + 3])));
-        } else if (i == 4) {
-          const float cm = half_max(fmaxf(fmaxf(cmp[0], cmp[1]), fmaxf(cmp[2], cmp[3]))) * scale_log2;
-          const float mn = fmaxf(mrun, cm);
-          mref = (mn == -INFINITY) ? 0.f : mn;
-          alpha = __builtin_amdgcn_exp2f(mrun - mref);
-          mrun = mn;
-        } else if (i < 10) {
-          pair(2 * (i - 5));
-          pair(2 * (i - 5) + 1);
-        } else {
-          pair(i);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(pb[i]));
-      asm volatile("" : "+v"(sum2));
-      lsum = lsum * alpha + (sum2[0] + sum2[1]);
-      if (__any(alpha != 1.f)) {
-#pragma unroll
-        for (int dt = 0; dt < D / 32; ++dt) acc[dt] *= alpha;
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) pbp[i] = pb[i];
+      if (k0 + TK - 1 > wave_kmin) w32_mask(s0, s1, kmax_col, k0, hi);
+      w32_softmax_under_pv(acc, s0, s1, pbp, smem + vprev * TILE, mrun, lsum, scale_log2, m, hi);
       vprev = gidx % NB;
     }
     if (active) {
-      // the last tile's P.V
-      const bf16* vt = smem + vprev * TILE;
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt) {
-#pragma unroll
-        for (int bh = 0; bh < 4; ++bh) {
-          const bf16x8 va = *reinterpret_cast<const bf16x8*>(
-              vt + 2 * BLK + (bh >> 1) * BLK + ((2 * (bh & 1) + hi) * D + 32 * dt + m) * 8);
-          acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pbp[bh], acc[dt], 0, 0, 0);
-        }
-      }
+      w32_pv_tail(acc, pbp, smem + vprev * TILE, m, hi);
       // output: lane (m, hi) holds dims 32 dt + 8 j + 4 hi + 0..3 of column m; for each pair of j
       // (2p, 2p + 1) the half-waves swap one 8-byte quad (v_permlane32_swap: lanes 32-63 of the
       // first operand <-> lanes 0-31 of the second), after which lane (m, hi) holds the 8 dims
@@ -1558,10 +1397,10 @@ static void launch_prefill(int g, int version, int max_q_len, int batch, int hkv
                            uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t bt, uintptr_t cu, uintptr_t sl,
                            int hq, int max_blocks, float sl2, uintptr_t pos, uintptr_t cs, int q_stride) {
   // version 3: the register-tiled kernel, two tiles per wave; 4: the LDS-shared kernel, two tiles per
-  // wave; 6: the LDS-shared kernel on 32x32x16 MFMAs, 8 waves x 32 columns (head_dim 128); 7: 6 with
-  // the previous tile's P.V overlapping this tile's softmax; 9: 7 persistent (one workgroup per CU)
+  // wave; 7: the LDS-shared kernel on 32x32x16 MFMAs, 8 waves x 32 columns (head_dim 128), the previous
+  // tile's P.V overlapping this tile's softmax; 9: 7 persistent (one workgroup per CU)
   const int nt = 2;
-  const int rows_per_wg = version >= 6 ? kW32Waves * (32 / g) : kWaves * (16 / g) * nt;
+  const int rows_per_wg = version >= 7 ? kW32Waves * (32 / g) : kWaves * (16 / g) * nt;
   const dim3 grid((max_q_len + rows_per_wg - 1) / rows_per_wg, hkv, batch);
   // version 9 (persistent): one workgroup per CU, 8 XCDs
   int cus = 0;
@@ -1572,30 +1411,23 @@ static void launch_prefill(int g, int version, int max_q_len, int batch, int hkv
     cus -= cus % 8;
     DLLM_HOST_CHECK(cus >= 8, "persistent prefill attention: CU count");
   }
-#define DLLM_PF(GG)                                                                                         \
-  do {                                                                                                      \
-    if (version == 9) {                                                                                     \
-      if constexpr (D == 128)                                                                               \
-        hipLaunchKernelGGL((attn_prefill_w32p_kernel<GG>), dim3(cus), dim3(kW32Waves * 64), 0, s, (bf16*)out, \
-                           (const bf16*)q, (const bf16*)k_cache, (const bf16*)v_cache, (const int32_t*)bt,    \
-                           (const int32_t*)cu, (const int32_t*)sl, hq, hkv, max_blocks, sl2,                 \
-                           (const int32_t*)pos, (const float*)cs, q_stride, (int)grid.x, batch * hkv);       \
-    } else if (version >= 6) {                                                                              \
-      if constexpr (D == 128) {                                                                             \
-        auto kern = version == 7 ? attn_prefill_w32_kernel<GG, true> : attn_prefill_w32_kernel<GG, false>;   \
-        hipLaunchKernelGGL(kern, grid, dim3(kW32Waves * 64), 0, s, (bf16*)out, (const bf16*)q,                \
-                           (const bf16*)k_cache, (const bf16*)v_cache, (const int32_t*)bt,                    \
-                           (const int32_t*)cu, (const int32_t*)sl, hq, hkv, max_blocks, sl2,                 \
-                           (const int32_t*)pos, (const float*)cs, q_stride);                                 \
-      }                                                                                                     \
-    } else if (version == 4)                                                                                \
-      hipLaunchKernelGGL((attn_prefill_lds_kernel<D, GG, 2>), grid, dim3(256), 0, s, (bf16*)out,              \
-                         (const bf16*)q, (const bf16*)k_cache, (const bf16*)v_cache, (const int32_t*)bt,      \
-                         (const int32_t*)cu, (const int32_t*)sl, hq, hkv, max_blocks, sl2,                   \
-                         (const int32_t*)pos, (const float*)cs, q_stride);                                   \
-    else                                                                                                    \
-      hipLaunchKernelGGL((attn_prefill2_kernel<D, GG, 2>), grid, dim3(256), 0, s, (bf16*)out, (const bf16*)q,  \
-                         (const bf16*)k_cache, (const bf16*)v_cache, (const int32_t*)bt, (const int32_t*)cu,   \
+  // the LDS kernels (4, 7, 9) share one signature; 9 appends its row-tile and group counts
+  auto go = [&](auto kern, dim3 gr, int threads, auto... tail) {
+    hipLaunchKernelGGL(kern, gr, dim3(threads), 0, s, (bf16*)out, (const bf16*)q, (const bf16*)k_cache,
+                       (const bf16*)v_cache, (const int32_t*)bt, (const int32_t*)cu, (const int32_t*)sl, hq, hkv,
+                       max_blocks, sl2, (const int32_t*)pos, (const float*)cs, q_stride, tail...);
+  };
+#define DLLM_PF(GG)                                                                                          \
+  do {                                                                                                       \
+    if (version == 9) {                                                                                      \
+      if constexpr (D == 128) go(attn_prefill_w32p_kernel<GG>, dim3(cus), kW32Waves * 64, (int)grid.x, batch * hkv); \
+    } else if (version == 7) {                                                                               \
+      if constexpr (D == 128) go(attn_prefill_w32_kernel<GG>, grid, kW32Waves * 64);                         \
+    } else if (version == 4)                                                                                 \
+      go(attn_prefill_lds_kernel<D, GG, 2>, grid, kWaves * 64);                                              \
+    else                                                                                                     \
+      hipLaunchKernelGGL((attn_prefill2_kernel<D, GG, 2>), grid, dim3(kWaves * 64), 0, s, (bf16*)out, (const bf16*)q, \
+                         (const bf16*)k_cache, (const bf16*)v_cache, (const int32_t*)bt, (const int32_t*)cu, \
                          (const int32_t*)sl, hq, hkv, max_blocks, sl2);                                      \
   } while (0)
   switch (g) {
@@ -1610,7 +1442,7 @@ static void launch_prefill(int g, int version, int max_q_len, int batch, int hkv
 }
 
 // positions / cos_sin / q_stride: q is the raw qkv projection (row stride q_stride elements) and RoPE
-// is applied in the kernel (LDS kernel, version 4); cos_sin = 0: q is [T, hq, D], rotated
+// is applied in the kernel (the LDS kernels: versions 4, 7 and 9); cos_sin = 0: q is [T, hq, D], rotated
 void paged_attention_prefill(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
                              uintptr_t block_tables, uintptr_t cu_seqlens_q, uintptr_t seq_lens, int batch,
                              int hq, int hkv, int d, int block_size, int max_blocks, int max_q_len, float scale,
@@ -1625,13 +1457,13 @@ void paged_attention_prefill(uintptr_t out, uintptr_t q, uintptr_t k_cache, uint
   const int G = hq / hkv;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const float sl2 = scale * 1.4426950408889634f;
-  // version (ops.prefill_attn_version): 4 = the LDS-shared kernel (short prompts); 6 / 7 / 9 = the
-  // 32x32x16 kernels (9, persistent, by default from 512 query rows; profiles/round6_attention.md);
+  // version (ops.prefill_attn_version): 4 = the LDS-shared kernel (short prompts); 7 / 9 = the
+  // 32x32x16 kernels (9, persistent, by default from 384 query rows; profiles/round6_attention.md);
   // 3 = the register-tiled kernel, which also serves block tables wider than the 32k tokens of
   // block ids the LDS kernels stage
-  DLLM_HOST_CHECK(version == 3 || version == 4 || version == 6 || version == 7 || version == 9,
-                  "prefill attention version 3, 4, 6, 7 or 9");
-  if (version >= 6 && (d != 128 || G > 16)) version = 4;           // the 32x32 kernels: head_dim 128, G | 32
+  DLLM_HOST_CHECK(version == 3 || version == 4 || version == 7 || version == 9,
+                  "prefill attention version 3, 4, 7 or 9");
+  if (version >= 7 && (d != 128 || G > 16)) version = 4;           // the 32x32 kernels: head_dim 128, G | 32
   if (version != 3 && max_blocks > kPfMaxChunks) version = 3;
   DLLM_HOST_CHECK(q_stride == hq * d || version != 3, "in-kernel RoPE / strided q: LDS kernels only (<= 32k context)");
   if (d == 128)

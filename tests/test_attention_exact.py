@@ -482,7 +482,7 @@ def test_decode_padded_bucket_bit_identical(cuda, form):
 
 
 # ------------------------------------------------------------------ prefill on the GPU
-_PREFILL_GPU = [(v, h) for h in PREFILL_HEADS for v in (3, 4, 6, 7, 9) if h[2] == 128 or v in (3, 4)]
+_PREFILL_GPU = [(v, h) for h in PREFILL_HEADS for v in (3, 4, 7, 9) if h[2] == 128 or v in (3, 4)]
 
 
 @pytest.mark.gpu
@@ -499,7 +499,7 @@ def test_prefill_exact(cuda, version, heads, form):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("form", FORMS)
-@pytest.mark.parametrize("version", [4, 6, 7, 9])
+@pytest.mark.parametrize("version", [4, 7, 9])
 def test_prefill_strided_q_exact(cuda, version, form):
     """cos_sin=None: q is read in place from the rows of the qkv projection."""
     c = prefill_case(form, 32, 8, 128)

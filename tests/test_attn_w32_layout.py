@@ -1,5 +1,5 @@
 """CPU check of the index algebra of the 32x32x16-MFMA prefill attention (attention.hip,
-attn_prefill_w32_kernel, prefill versions 6 / 7): a numpy model of v_mfma_f32_32x32x16_bf16's operand
+attn_prefill_w32_kernel, prefill versions 7 / 9): a numpy model of v_mfma_f32_32x32x16_bf16's operand
 and result layouts, fed exactly as the kernel feeds it -- K rows at w32_krow(m) of the krow32-permuted
 cache block, the P.V B operand taken straight from 8 consecutive score registers, the V^T A operand
 read from key group 2 h + hi of the [4][D][8] V^T block -- reproduces softmax(Q K^T) V of one tile.

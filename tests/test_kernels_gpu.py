@@ -174,7 +174,7 @@ def test_paged_attention_decode_fused_rope(cuda, hq, hkv, d, lens, rope):
     torch.testing.assert_close(v1.float(), v2, atol=0, rtol=0)
 
 
-@pytest.mark.parametrize("version", ["3", "4", "6", "7", "9"])
+@pytest.mark.parametrize("version", ["3", "4", "7", "9"])
 @pytest.mark.parametrize("hq,hkv,d", [(32, 8, 128), (64, 8, 128), (12, 12, 64), (8, 4, 64), (16, 16, 128),
                                       (32, 2, 128)])
 def test_paged_attention_prefill(cuda, hq, hkv, d, version):
@@ -188,9 +188,11 @@ def test_paged_attention_prefill(cuda, hq, hkv, d, version):
     out = ops.paged_attention_prefill(q, k, v, bt, cu, sl, scale, version=int(version))
     expect = ref.paged_attention_prefill(q.float(), k.float(), v.float(), bt, cu, sl, scale)
     torch.testing.assert_close(out.float(), expect, atol=2e-2, rtol=2e-2)
+    with pytest.raises(RuntimeError):       # version 6 is removed: the launcher's precondition, before any launch
+        ops.paged_attention_prefill(q, k, v, bt, cu, sl, scale, version=6)
 
 
-@pytest.mark.parametrize("version", ["3", "4", "6", "7", "9"])
+@pytest.mark.parametrize("version", ["3", "4", "7", "9"])
 def test_paged_attention_prefill_long(cuda, version):
     """Long prompts: > 64 KV chunks per sequence (block-id reloads), many workgroups per
     (sequence, kv head), a chunked prefill that starts mid-block."""
@@ -275,7 +277,7 @@ def _splitk_qkv_bit_exact(b, splits, hq, hkv, d, hidden):
     torch.testing.assert_close(v1, v2, atol=0, rtol=0)
 
 
-@pytest.mark.parametrize("version", [4, 6, 7, 9])
+@pytest.mark.parametrize("version", [4, 7, 9])
 @pytest.mark.parametrize("hq,hkv,d", [(32, 8, 128), (8, 4, 64)])
 def test_prefill_attention_with_q_rope_in_kernel(cuda, hq, hkv, d, version):
     """knobs.prefill_fused_rope: rope_cache_append(write_q=False) appends K / V only and the LDS prefill

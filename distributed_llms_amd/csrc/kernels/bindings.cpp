@@ -18,6 +18,8 @@ PYBIND11_MODULE(_C_kernels, m) {
   m.def("silu_mul", &dllm::silu_mul);
   m.def("argmax", &dllm::argmax);
   m.def("sample_rows", &dllm::sample_rows);
+  m.def("token_logprobs", &dllm::token_logprobs);
+  m.attr("MAX_LOGPROBS") = dllm::kMaxLogprobs;
   m.def("add_inplace", &dllm::add_inplace);
   m.def("moe_route", &dllm::moe_route);
   m.def("moe_grouped_gemm", &dllm::moe_grouped_gemm);

@@ -25,6 +25,11 @@ void argmax(uintptr_t out, uintptr_t logits, int rows, int vocab, long row_strid
 // uniforms [rows] f32 or 0 (test hook: replaces the Philox draw); all on the device
 void sample_rows(uintptr_t out_ids, uintptr_t logits, int rows, int vocab, long row_stride, uintptr_t params,
                  uintptr_t seeds, uintptr_t pos, uintptr_t uniforms, uintptr_t stream);
+// sampler.hip: log-probabilities of the model's distribution.  ids [rows] i32 (the chosen token), want [rows] i32
+// (-1: skip the row, else how many top entries, at most n_max); chosen [rows] f32, top_ids / top_lp [rows, n_max]
+constexpr int kMaxLogprobs = 20;
+void token_logprobs(uintptr_t chosen, uintptr_t top_ids, uintptr_t top_lp, uintptr_t logits, int rows, int vocab,
+                    long row_stride, uintptr_t ids, uintptr_t want, int n_max, uintptr_t stream);
 
 void splitk_add_rms_norm(uintptr_t y, uintptr_t residual, uintptr_t ws, int S, int M, int N, uintptr_t w, float eps,
                          uintptr_t stream);

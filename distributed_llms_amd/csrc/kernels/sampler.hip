@@ -160,39 +160,11 @@ __device__ __forceinline__ void for_iters(int nit, F&& f) {
     if (it < nit) f(it);
 }
 
-struct SampleShared {
-  uint32_t cnt_h[256 * kCopies];   // histogram copies: [bin][lane & 15]
-  u64 mass_h[256 * kCopies];       // the final pass reuses the first 256 entries as per-wave sums
-  uint32_t cnt1[256], cnt2[256];   // level 1 (high byte) and level 2 (low byte of one bin)
-  u64 mass1[256], mass2[256];
-  u64 red[16];
-};
-
-__device__ __forceinline__ void sample_row(SampleShared& sh, int32_t* __restrict__ out,
-                                           const uint16_t* __restrict__ row, int vocab, bool aligned, int temp_e4,
-                                           int top_k, int top_p_e4, u64 seed, int pos, const float* uniform) {
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int ngroups = (vocab + 7) >> 3;
-  const int nit = (ngroups + kThreads - 1) / kThreads;
-
-  u32x4 x[kRegIters];
-  // The passes below recompute keys and masses from x on purpose.  Without this the compiler
-  // treats them as common to all passes (and invariant in the threshold loop) and tries to keep
-  // all 128 of a thread's masses live: hundreds of spills.  An empty asm makes x opaque per pass.
-  auto launder = [&]() {
-#pragma unroll
-    for (int it = 0; it < kRegIters; ++it) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t t = x[it][j];
-        asm volatile("" : "+v"(t));
-        x[it][j] = t;
-      }
-    }
-  };
-
-  // ---- pass 1: the only read of the row; max key and its first index
-  u64 best = 0;   // key << 32 | ~index: the larger key, then the smaller index, wins a plain max
+// Pass 1 of both kernels, the only read of the row: its keys into x, and the thread's best
+// key << 32 | ~index (the larger key, then the smaller index, wins a plain max; 0: no entry).
+__device__ __forceinline__ u64 load_row_keys(u32x4 (&x)[kRegIters], const uint16_t* __restrict__ row, int vocab,
+                                             bool aligned, int tid, int ngroups, int nit) {
+  u64 best = 0;
   if (aligned) {
     // every full group's 16-byte load is issued before the first conversion waits on one
     const int nfull = vocab >> 3;
@@ -232,6 +204,58 @@ __device__ __forceinline__ void sample_row(SampleShared& sh, int32_t* __restrict
       }
     }
   });
+  return best;
+}
+
+// An empty asm per word makes x opaque to the compiler at this point: what a pass derives from x
+// (keys, masses, index words) is then not common to the passes before and after it
+__device__ __forceinline__ void launder_keys(u32x4 (&x)[kRegIters]) {
+#pragma unroll
+  for (int it = 0; it < kRegIters; ++it) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint32_t t = x[it][j];
+      asm volatile("" : "+v"(t));
+      x[it][j] = t;
+    }
+  }
+}
+
+// floor(2^40 * exp2((val(k) - lmax) * (c + c_lo))) of key k; exactly 2^40 for the row's maximum
+__device__ __forceinline__ u64 mass_q40(uint32_t k, uint32_t maxkey, float lmax, float c, float c_lo) {
+  if (k == maxkey) return 1ull << 40;
+  // floor(w * 2^40) from two 20-bit halves (both products and the remainder are exact in f32)
+  const float d = val_of(k) - lmax;
+  const float arg = d == -INFINITY ? d : fmaf(d, c, d * c_lo);   // -inf * c_lo may be +inf
+  const float w20 = __builtin_amdgcn_exp2f(arg) * 0x1p20f;
+  const uint32_t hi = (uint32_t)w20;
+  const uint32_t lo = (uint32_t)((w20 - (float)hi) * 0x1p20f);
+  return ((u64)hi << 20) | lo;
+}
+
+struct SampleShared {
+  uint32_t cnt_h[256 * kCopies];   // histogram copies: [bin][lane & 15]
+  u64 mass_h[256 * kCopies];       // the final pass reuses the first 256 entries as per-wave sums
+  uint32_t cnt1[256], cnt2[256];   // level 1 (high byte) and level 2 (low byte of one bin)
+  u64 mass1[256], mass2[256];
+  u64 red[16];
+};
+
+__device__ __forceinline__ void sample_row(SampleShared& sh, int32_t* __restrict__ out,
+                                           const uint16_t* __restrict__ row, int vocab, bool aligned, int temp_e4,
+                                           int top_k, int top_p_e4, u64 seed, int pos, const float* uniform) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int ngroups = (vocab + 7) >> 3;
+  const int nit = (ngroups + kThreads - 1) / kThreads;
+
+  u32x4 x[kRegIters];
+  // The passes below recompute keys and masses from x on purpose.  Without this the compiler
+  // treats them as common to all passes (and invariant in the threshold loop) and tries to keep
+  // all 128 of a thread's masses live: hundreds of spills.  An empty asm makes x opaque per pass.
+  auto launder = [&]() { launder_keys(x); };
+
+  // ---- pass 1: the only read of the row; max key and its first index
+  u64 best = load_row_keys(x, row, vocab, aligned, tid, ngroups, nit);
   best = wave_max_u64(best);
   if (lane == 0) sh.red[wid] = best;
   __syncthreads();
@@ -251,16 +275,7 @@ __device__ __forceinline__ void sample_row(SampleShared& sh, int32_t* __restrict
   // log2(e) / T as a float pair: the exponent's argument then carries one rounding, not two
   const double cd = 1.4426950408889634 * 1e4 / (double)temp_e4;
   const float c = (float)cd, c_lo = (float)(cd - (double)c);
-  auto massq = [&](uint32_t k) -> u64 {
-    if (k == maxkey) return 1ull << 40;
-    // floor(w * 2^40) from two 20-bit halves (both products and the remainder are exact in f32)
-    const float d = val_of(k) - lmax;
-    const float arg = d == -INFINITY ? d : fmaf(d, c, d * c_lo);   // -inf * c_lo may be +inf
-    const float w20 = __builtin_amdgcn_exp2f(arg) * 0x1p20f;
-    const uint32_t hi = (uint32_t)w20;
-    const uint32_t lo = (uint32_t)((w20 - (float)hi) * 0x1p20f);
-    return ((u64)hi << 20) | lo;
-  };
+  auto massq = [&](uint32_t k) -> u64 { return mass_q40(k, maxkey, lmax, c, c_lo); };
 
   // One 256-bin histogram over the keys >= minkey: of their high byte (sel < 0), or of the low
   // byte of those whose high byte is sel.  Counts (top-k) or masses (top-p): the count passes need
@@ -450,6 +465,167 @@ __global__ void __launch_bounds__(1024) sample_rows_kernel(int32_t* __restrict__
              uniforms ? uniforms + b : nullptr);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-token log-probabilities of the model's distribution (no temperature, top-k or top-p):
+// ops/reference.py token_logprobs is the same thing in float64.
+//   m = row maximum (NaN counts as -inf), Z = sum_j exp(x_j - m) with exactly 1 for x_j == m,
+//   lp_i = (x_i - m) - ln Z with x_i - m = 0 where x_i == m; every lp is -inf when m is -inf
+//   want < 0   the row is skipped: chosen = 0, top_ids = -1, top_lp = 0
+//   want = n   chosen = lp[ids[b]] (-inf for an id outside the row); the first min(n, n_max, vocab)
+//              top slots hold the largest entries by decreasing value, then increasing index; the
+//              rest hold -1 / 0
+// Z is the integer sum of the sampler's 2^40-scaled masses at T = 1, so a row's outputs do not
+// depend on its batch, its row index or the launch.  The top entries come from n rounds of a
+// workgroup max over key << 32 | ~index: unique per entry, so the order needs no tie rule.  A
+// thread keeps its best composite below the last winner, so only the winner's owner has to look at
+// its 128 entries again: it hands them to its wave through LDS, two entries per lane (one lane
+// walking all 128 measured 4.5 us per round; profiles/logprobs.md).
+struct LogprobShared {
+  u64 red[2][16];   // alternating buffers: one barrier per round
+  u64 zred[16];
+  float lnz;
+  uint32_t scan[16][kRegIters * 4];   // per wave: the owner's packed keys
+};
+
+__global__ void __launch_bounds__(1024) token_logprobs_kernel(float* __restrict__ chosen, int32_t* __restrict__ top_ids,
+                                                              float* __restrict__ top_lp,
+                                                              const bf16* __restrict__ logits, int vocab,
+                                                              long row_stride, const int32_t* __restrict__ ids,
+                                                              const int32_t* __restrict__ want, int n_max) {
+  __shared__ LogprobShared sh;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int n = want[b];
+  n = n > n_max ? n_max : n;
+  n = n > vocab ? vocab : n;
+  int32_t* tids = top_ids + (size_t)b * n_max;
+  float* tlps = top_lp + (size_t)b * n_max;
+  if (tid < n_max && tid >= n) {   // n < 0: every slot
+    tids[tid] = -1;
+    tlps[tid] = 0.f;
+  }
+  if (n < 0) {   // workgroup-uniform
+    if (tid == 0) chosen[b] = 0.f;
+    return;
+  }
+
+  const uint16_t* row = reinterpret_cast<const uint16_t*>(logits) + (size_t)b * row_stride;
+  const bool aligned = (((uintptr_t)row) & 15) == 0;
+  const int ngroups = (vocab + 7) >> 3;
+  const int nit = (ngroups + kThreads - 1) / kThreads;
+
+  u32x4 x[kRegIters];
+  // as in sample_row: x opaque per pass, so no pass's per-entry values are kept live for another
+  auto launder = [&]() { launder_keys(x); };
+  // the workgroup's largest composite; round r uses buffer r & 1
+  auto block_max = [&](u64 v, int buf) -> u64 {
+    v = wave_max_u64(v);
+    if (lane == 0) sh.red[buf][wid] = v;
+    __syncthreads();
+    u64 m = sh.red[buf][0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) m = sh.red[buf][w] > m ? sh.red[buf][w] : m;
+    return uni(m);
+  };
+
+  // ---- pass 1: the only read of the row; the thread's best entry, then the row's
+  u64 mine = load_row_keys(x, row, vocab, aligned, tid, ngroups, nit);
+  u64 win = block_max(mine, 0);
+  const uint32_t maxkey = (uint32_t)(win >> 32);
+  const bool dead = maxkey == kKeyNegInf;   // no entry above -inf: every lp is -inf
+  const float lmax = val_of(maxkey);
+
+  // ---- Z and ln Z
+  if (!dead) {
+    const double cd = 1.4426950408889634;   // log2(e): T = 1
+    const float c = (float)cd, c_lo = (float)(cd - (double)c);
+    u64 z = 0;
+    launder();
+    for_iters(nit, [&](int it) {
+      const int g = it * kThreads + tid;
+      if (g < ngroups) {
+        const u32x4 xg = x[it];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const uint32_t k = key_at(xg, j);
+          if (k != 0) z += mass_q40(k, maxkey, lmax, c, c_lo);
+        }
+      }
+    });
+    z = wave_sum_u64(z);
+    if (lane == 0) sh.zred[wid] = z;
+    __syncthreads();
+    if (tid == 0) {
+      u64 zt = 0;
+#pragma unroll
+      for (int w = 0; w < 16; ++w) zt += sh.zred[w];
+      sh.lnz = (float)log((double)zt * 0x1p-40);   // Z >= 1: the maximum's own mass
+    }
+    __syncthreads();
+  }
+  const float lnz = dead ? 0.f : sh.lnz;
+  auto lp_of = [&](uint32_t k) -> float {
+    if (dead) return -INFINITY;
+    const float d = k == maxkey ? 0.f : val_of(k) - lmax;   // -inf below a +inf maximum
+    return d - lnz;
+  };
+
+  // ---- the chosen token: its owner holds the key in registers
+  const int id = ids[b];
+  if (id < 0 || id >= vocab) {
+    if (tid == 0) chosen[b] = -INFINITY;
+  } else if (tid == ((id >> 3) & (kThreads - 1))) {
+    const int it_c = (id >> 3) / kThreads, j_c = id & 7;
+    uint32_t kc = 0;
+    for_iters(nit, [&](int it) {
+      if (it != it_c) return;
+      const u32x4 xg = x[it];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j == j_c) kc = key_at(xg, j);
+    });
+    chosen[b] = lp_of(kc);
+  }
+
+  // ---- the n largest entries
+#pragma unroll 1
+  for (int r = 0; r < n; ++r) {
+    if (tid == 0) {
+      tids[r] = (int)~(uint32_t)win;
+      tlps[r] = lp_of((uint32_t)(win >> 32));
+    }
+    if (r + 1 == n) break;
+    const u64 own = __ballot(mine == win);   // one lane of one wave
+    if (own != 0) {                           // wave-uniform: the owner's wave finds its next best entry
+      const int src = __ffsll((long long)own) - 1;
+      uint32_t* sc = sh.scan[wid];
+      if (lane == src) {
+#pragma unroll
+        for (int it = 0; it < kRegIters; ++it) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) sc[it * 4 + j] = x[it][j];   // zeros past the row
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      // lane l: dword l, the entries 2 * (l & 3) and + 1 of the owner's group in iteration l >> 2
+      const uint32_t d = sc[lane];
+      const int g = (lane >> 2) * kThreads + (wid * 64 + src);
+      u64 nb = 0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const uint32_t k = h ? d >> 16 : d & 0xFFFFu;
+        const u64 cand = ((u64)k << 32) | (uint32_t)~(uint32_t)(g * 8 + 2 * (lane & 3) + h);
+        if (k != 0 && cand < win && cand > nb) nb = cand;
+      }
+      nb = wave_max_u64(nb);
+      if (lane == src) mine = nb;
+    }
+    win = block_max(mine, (r + 1) & 1);
+  }
+}
+
 }  // namespace
 
 void sample_rows(uintptr_t out_ids, uintptr_t logits, int rows, int vocab, long row_stride, uintptr_t params,
@@ -461,6 +637,18 @@ void sample_rows(uintptr_t out_ids, uintptr_t logits, int rows, int vocab, long 
   hipLaunchKernelGGL(sample_rows_kernel, dim3(rows), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream),
                      (int32_t*)out_ids, (const bf16*)logits, vocab, row_stride, (const int32_t*)params,
                      (const u64*)seeds, (const int32_t*)pos, (const float*)uniforms);
+  DLLM_HIP_CHECK(hipGetLastError());
+}
+
+void token_logprobs(uintptr_t chosen, uintptr_t top_ids, uintptr_t top_lp, uintptr_t logits, int rows, int vocab,
+                    long row_stride, uintptr_t ids, uintptr_t want, int n_max, uintptr_t stream) {
+  if (rows == 0) return;
+  DLLM_HOST_CHECK(vocab >= 1 && vocab <= kRegIters * kThreads * 8, "token_logprobs: vocab must be in [1, 131072]");
+  DLLM_HOST_CHECK(row_stride >= 0, "token_logprobs: row stride must not be negative");
+  DLLM_HOST_CHECK(n_max >= 0 && n_max <= kMaxLogprobs, "token_logprobs: n_max must be in [0, 20]");
+  hipLaunchKernelGGL(token_logprobs_kernel, dim3(rows), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream),
+                     (float*)chosen, (int32_t*)top_ids, (float*)top_lp, (const bf16*)logits, vocab, row_stride,
+                     (const int32_t*)ids, (const int32_t*)want, n_max);
   DLLM_HIP_CHECK(hipGetLastError());
 }
 

@@ -41,6 +41,7 @@ struct SeqRec {
   int32_t last = 0;       // newest known token
   int32_t samp[3] = {0, 0, 10000};   // temperature * 1e4, top_k, top_p * 1e4
   int32_t seed[2] = {0, 0};          // low / high word of the 64-bit sampling seed
+  int32_t num_logprobs = -1;         // HostBatch.logprobs word of the row: -1 = the request did not ask
   bool running = true;
   int reason = R_NONE;
   std::vector<int32_t> out;     // tokens generated while registered here
@@ -61,7 +62,7 @@ class SlotBatcher {
 
   // Register a sequence that finished its prefill and keeps decoding in `slot`.
   void admit(int slot, int64_t id, int32_t len, int32_t last, int32_t remaining, int32_t eos, int32_t temp_e4,
-             int32_t top_k, int32_t top_p_e4, int32_t seed_lo, int32_t seed_hi) {
+             int32_t top_k, int32_t top_p_e4, int32_t seed_lo, int32_t seed_hi, int32_t num_logprobs) {
     check_slot(slot);
     if (recs_.count(id)) throw std::invalid_argument("sequence already registered");
     if (remaining <= 0 || len >= max_seq_len_ || len < 1) throw std::invalid_argument("admit: nothing to decode");
@@ -76,6 +77,7 @@ class SlotBatcher {
     r.samp[2] = top_p_e4;
     r.seed[0] = seed_lo;
     r.seed[1] = seed_hi;
+    r.num_logprobs = num_logprobs < 0 ? -1 : num_logprobs;
     recs_.emplace(id, std::move(r));
     order_[slot].push_back(id);
   }
@@ -154,8 +156,13 @@ class SlotBatcher {
 
     const int b = (int)rows.size();
     bool has_s = false;
-    for (int64_t id : rows) has_s |= rec(id).samp[0] > 0;
-    const size_t n = HDR + 3 * (size_t)b + b + (b + 1) + (size_t)b * max_blocks + b + (has_s ? 5 * (size_t)b : 0);
+    bool has_lp = false;   // the logprobs section only when a row of the step asked
+    for (int64_t id : rows) {
+      has_s |= rec(id).samp[0] > 0;
+      has_lp |= rec(id).num_logprobs >= 0;
+    }
+    const size_t n = HDR + 3 * (size_t)b + b + (b + 1) + (size_t)b * max_blocks + b + (has_s ? 5 * (size_t)b : 0) +
+                     (has_lp ? (size_t)b : 0);
     py::array_t<int32_t> packed((py::ssize_t)n);
     int32_t* p = packed.mutable_data();
     std::fill(p, p + HDR, 0);
@@ -168,6 +175,7 @@ class SlotBatcher {
     int32_t* lidx = bt + (size_t)b * max_blocks;
     int32_t* samp = lidx + b;
     int32_t* seeds = samp + 3 * (size_t)b;    // [b, 2], written whenever samp is (header word 10)
+    int32_t* lps = has_s ? seeds + 2 * (size_t)b : samp;   // [b], header word 11
     const int bs = bm_.block_size();
     int32_t max_ctx = 0;
     for (int i = 0; i < b; ++i) {
@@ -190,6 +198,7 @@ class SlotBatcher {
         std::copy(r.samp, r.samp + 3, samp + 3 * (size_t)i);
         std::copy(r.seed, r.seed + 2, seeds + 2 * (size_t)i);
       }
+      if (has_lp) lps[i] = r.num_logprobs;
       max_ctx = std::max(max_ctx, ctx);
       r.pend += 1;
     }
@@ -204,6 +213,7 @@ class SlotBatcher {
     p[7] = step_id;
     p[8] = has_s ? 1 : 0;
     p[10] = has_s ? 1 : 0;   // sample_seeds follow the sampling block
+    p[11] = has_lp ? 1 : 0;  // logprobs follow the seeds
 
     py::array_t<int64_t> rows_a(b);
     std::copy(rows.begin(), rows.end(), rows_a.mutable_data());
@@ -360,7 +370,7 @@ void register_slot_batcher(py::module_& m) {
       .def_property_readonly("max_seq_len", &SlotBatcher::max_seq_len)
       .def("admit", &SlotBatcher::admit, py::arg("slot"), py::arg("seq_id"), py::arg("length"), py::arg("last_token"),
            py::arg("remaining"), py::arg("eos") = -1, py::arg("temp_e4") = 0, py::arg("top_k") = 0,
-           py::arg("top_p_e4") = 10000, py::arg("seed_lo") = 0, py::arg("seed_hi") = 0)
+           py::arg("top_p_e4") = 10000, py::arg("seed_lo") = 0, py::arg("seed_hi") = 0, py::arg("num_logprobs") = -1)
       .def("num_running", &SlotBatcher::num_running)
       .def("num_running_total", &SlotBatcher::num_running_total)
       .def("min_running", &SlotBatcher::min_running)

@@ -43,6 +43,10 @@ class HostBatch:
     # [B, 2] int32: low and high word of each row's 64-bit sampling seed (None: unseeded); packed
     # after ``sampling`` with header word 10 set
     sample_seeds: Optional[np.ndarray] = None
+    # [B] int32: how many top log-probabilities each row reports next to its chosen token's (0: the
+    # chosen token's only, -1: the row did not ask); None when no row asks -- the packed array is
+    # then what it was without the field.  Packed after ``sample_seeds`` with header word 11 set
+    logprobs: Optional[np.ndarray] = None
 
     @property
     def num_tokens(self) -> int:
@@ -63,14 +67,17 @@ class HostBatch:
         mb = self.block_tables.shape[1] if self.block_tables.ndim == 2 else 0
         has_s = 1 if self.sampling is not None else 0
         has_seeds = 1 if self.sample_seeds is not None else 0
+        has_lp = 1 if self.logprobs is not None else 0
         hdr = np.array([1 if self.is_prefill else 0, t, b, mb, self.max_q_len, self.max_ctx, self.slot,
-                        self.step_id, has_s, self.num_decode, has_seeds] + [0] * 5, dtype=np.int32)
+                        self.step_id, has_s, self.num_decode, has_seeds, has_lp] + [0] * 4, dtype=np.int32)
         parts = [hdr, self.ids, self.positions, self.slots, self.seq_lens, self.cu_seqlens,
                  self.block_tables.reshape(-1), self.logits_idx]
         if has_s:
             parts.append(self.sampling.reshape(-1))
         if has_seeds:
             parts.append(self.sample_seeds.reshape(-1))
+        if has_lp:
+            parts.append(self.logprobs)
         return np.concatenate([p.astype(np.int32, copy=False).reshape(-1) for p in parts])
 
     def sampling_args(self) -> dict:
@@ -101,8 +108,9 @@ class HostBatch:
         lidx = take(b)
         samp = take(3 * b).reshape(b, 3) if has_s else None
         seeds = take(2 * b).reshape(b, 2) if int(hdr[10]) else None
+        lps = take(b) if int(hdr[11]) else None
         return HostBatch(bool(pf), ids, pos, slots, seq_lens, cu, bt, lidx, mq, mc, slot, sid, samp, raw=arr,
-                         num_decode=nd, sample_seeds=seeds)
+                         num_decode=nd, sample_seeds=seeds, logprobs=lps)
 
 
 def next_pow2(x: int, lo: int = 1) -> int:
@@ -170,8 +178,11 @@ def build_host_batch(step: Step, bm, block_size: int, max_blocks: Optional[int] 
         sampling = np.array([[int(round(s.params.temperature * 1e4)), int(s.params.top_k),
                               int(round(s.params.top_p * 1e4))] for s in seqs], dtype=np.int32)
         seeds = np.array([split_seed(s.seed) for s in seqs], dtype=np.int32).reshape(b, 2)
+    lps = None
+    if any(s.params.logprobs is not None for s in seqs):
+        lps = np.fromiter((s.num_logprobs for s in seqs), dtype=np.int32, count=b)
     return HostBatch(step.is_prefill, ids, positions, slots, seq_lens, cu, bt, logits_idx, max_q_len,
-                     max_ctx, step.slot, step_id, sampling, sample_seeds=seeds)
+                     max_ctx, step.slot, step_id, sampling, sample_seeds=seeds, logprobs=lps)
 
 
 def merge_mixed(dec: HostBatch, pre: HostBatch, slot: int, step_id: int) -> HostBatch:
@@ -195,13 +206,18 @@ def merge_mixed(dec: HostBatch, pre: HostBatch, slot: int, step_id: int) -> Host
         seeds = np.concatenate([dec.sample_seeds if dec.sample_seeds is not None else np.zeros((nd, 2), np.int32),
                                 pre.sample_seeds if pre.sample_seeds is not None
                                 else np.zeros((pre.num_seqs, 2), np.int32)]).astype(np.int32)
+    lps = None
+    if dec.logprobs is not None or pre.logprobs is not None:
+        lps = np.concatenate([dec.logprobs if dec.logprobs is not None else np.full(nd, -1, np.int32),
+                              pre.logprobs if pre.logprobs is not None
+                              else np.full(pre.num_seqs, -1, np.int32)]).astype(np.int32)
     return HostBatch(True, np.concatenate([dec.ids, pre.ids]).astype(np.int32),
                      np.concatenate([dec.positions, pre.positions]).astype(np.int32),
                      np.concatenate([dec.slots, pre.slots]).astype(np.int32),
                      np.concatenate([dec.seq_lens, pre.seq_lens]).astype(np.int32), cu, bt,
                      np.concatenate([np.arange(nd, dtype=np.int32), pre.logits_idx.astype(np.int32) + nd]),
                      max(1, pre.max_q_len), max(dec.max_ctx, pre.max_ctx), slot, step_id, sampling, num_decode=nd,
-                     sample_seeds=seeds)
+                     sample_seeds=seeds, logprobs=lps)
 
 
 def build_decode_batch(seq_ids: np.ndarray, seq_lens: np.ndarray, bm, block_size: int, max_blocks: int,

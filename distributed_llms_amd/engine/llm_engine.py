@@ -23,9 +23,9 @@ from ..models.stage import ModelStage
 from .batch import build_host_batch
 from .graphs import SCRATCH_SEQ_ID
 from .runner import StageRunner
-from .sampler import sample
+from .sampler import ids_message_len, max_ids_message_len, sample_step, unpack_ids_message
 from .scheduler import Scheduler, Step
-from .sequence import SamplingParams, Sequence, request_seed
+from .sequence import SamplingParams, Sequence, request_seed, validate_logprobs
 
 log = logging.getLogger("dllm.engine")
 
@@ -93,7 +93,8 @@ class LLMEngine:
             dev = self.stage.device
             self.streams = [torch.cuda.Stream(dev) for _ in range(self.num_slots)]
             # two pinned token buffers + events per slot: with lookahead two steps of a slot are in flight
-            self.tok_host = [[torch.empty(max(ecfg.max_batch, 1), dtype=torch.int32).pin_memory() for _ in range(2)]
+            self.tok_host = [[torch.empty(max_ids_message_len(max(ecfg.max_batch, 1)), dtype=torch.int32).pin_memory()
+                              for _ in range(2)]
                              for _ in range(self.num_slots)]
             self.events = [[torch.cuda.Event() for _ in range(2)] for _ in range(self.num_slots)]
             self.tok_i = [0] * self.num_slots
@@ -101,8 +102,12 @@ class LLMEngine:
     # ------------------------------------------------------------ requests
     def add_request(self, prompt: List[int], params: Optional[SamplingParams] = None,
                     request_id: Optional[str] = None) -> Sequence:
-        seq = Sequence(list(prompt), params or SamplingParams(), eos_token_id=self.mcfg.eos_token_id,
-                       request_id=request_id)
+        params = params or SamplingParams()
+        if validate_logprobs(params.logprobs) is not None and self.tp is not None:
+            # the tensor-parallel lanes draw with a distributed arg-max over vocabulary shards;
+            # log-probabilities there need a distributed log-sum-exp
+            raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
+        seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id)
         seq.seed = request_seed(seq.params, self._seed_rng)
         self.scheduler.add(seq)
         return seq
@@ -125,16 +130,24 @@ class LLMEngine:
 
     def execute_step(self, step: Step) -> List[int]:
         """Synchronous execution of one step (CPU path / tests)."""
+        return self._execute(step)[0].tolist()
+
+    def _execute(self, step: Step):
+        """Synchronous execution of one step -> (ids, logprobs) on the host, as
+        ``Scheduler.complete`` takes them (``logprobs`` None unless a row of the step asked)."""
         hb = self._host_batch(step)
         logits = self.runner.execute(hb, slot=step.slot)
-        ids = self._sample(logits, hb)
-        return ids.cpu().tolist()
+        ids, msg = self._sample(logits, hb)
+        if msg is None:
+            return ids.cpu().numpy(), None
+        return unpack_ids_message(msg.cpu().numpy(), hb)
 
     def _sample(self, logits, hb):
+        """(ids, ids message or None): engine/sampler.py sample_step."""
         if self.tp is not None:
             from ..parallel.tensor_parallel import tp_sample
-            return tp_sample(logits, self.tp, hb.sampling_args())
-        return sample(logits, **hb.sampling_args())
+            return tp_sample(logits, self.tp, hb.sampling_args()), None
+        return sample_step(logits, hb)
 
     def _launch(self, step: Step, hb, slot: int, ids_src: Optional[torch.Tensor] = None, keep=None):
         """``ids_src`` (lookahead): the in-flight step's sampled ids on the device, rows ``keep``
@@ -151,11 +164,12 @@ class LLMEngine:
                     0, torch.from_numpy(np.asarray(keep, dtype=np.int64)).pin_memory().to(ids_src.device,
                                                                                           non_blocking=True))
             logits = self.runner.execute(hb, slot=slot, ids_dev=ids_dev)
-            ids = self._sample(logits, hb)
+            ids, msg = self._sample(logits, hb)
+            out = ids if msg is None else msg
             n = ids.shape[0]
-            self.tok_host[slot][i][:n].copy_(ids, non_blocking=True)
+            self.tok_host[slot][i][:out.shape[0]].copy_(out, non_blocking=True)
             self.events[slot][i].record(s)
-        self.inflight.append((step, slot, n, i, ids))
+        self.inflight.append((step, slot, n, i, ids, None if msg is None else hb))
         self.busy[slot] = True
 
     def _issue(self, slot: int) -> bool:
@@ -174,7 +188,7 @@ class LLMEngine:
         needs the host first: waiting requests, non-decode steps, KV growth failures."""
         if not self.lookahead or self.scheduler.waiting or not self.inflight:
             return False
-        prev, pslot, pn, _, pids = self.inflight[-1]
+        prev, pslot, pn, _, pids, _ = self.inflight[-1]
         if pslot != slot or prev.is_prefill or len(self.inflight) > 1:
             return False
         step = self.scheduler.schedule_lookahead(slot)      # native: rows, packed metadata, keep
@@ -186,9 +200,13 @@ class LLMEngine:
         return True
 
     def _complete_oldest(self):
-        step, slot, n, i, _ = self.inflight.popleft()
+        step, slot, n, i, _, lp_hb = self.inflight.popleft()
         self.events[slot][i].synchronize()
-        self.scheduler.complete(step, self.tok_host[slot][i][:n].numpy(), time.perf_counter())
+        if lp_hb is None:
+            self.scheduler.complete(step, self.tok_host[slot][i][:n].numpy(), time.perf_counter())
+        else:     # a row of the step asked for log-probabilities: the pinned buffer holds its ids message
+            toks, lps = unpack_ids_message(self.tok_host[slot][i][:ids_message_len(lp_hb)].numpy(), lp_hb)
+            self.scheduler.complete(step, toks, time.perf_counter(), lps)
         self.busy[slot] = any(e[1] == slot for e in self.inflight)
 
     def step(self) -> List[Sequence]:
@@ -196,8 +214,8 @@ class LLMEngine:
         if self.stage.device.type != "cuda":
             st = self.scheduler.schedule(0)
             if st is not None:
-                toks = self.execute_step(st)
-                self.scheduler.complete(st, toks, time.perf_counter())
+                toks, lps = self._execute(st)
+                self.scheduler.complete(st, toks, time.perf_counter(), lps)
             return self.scheduler.pop_finished()
         issued = False
         for slot in range(self.num_slots):

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .sequence import split_seed
+from .sequence import MAX_LOGPROBS, split_seed
 
 
 def sample(logits: torch.Tensor, temperatures: Optional[Seq[float]] = None, top_k: Optional[Seq[int]] = None,
@@ -51,7 +51,9 @@ def sample(logits: torch.Tensor, temperatures: Optional[Seq[float]] = None, top_
     return torch.where(is_greedy, greedy, drawn)
 
 
-_STAGE_DEPTH = 4      # pinned buffers per device: more than the steps one slot keeps in flight
+# pinned buffers per device: more than the uploads of the steps one slot keeps in flight (a step
+# makes up to two: the sampler's parameters and, when a row asks, the logprobs counts)
+_STAGE_DEPTH = 8
 _stages: dict = {}
 
 
@@ -95,6 +97,60 @@ def _sample_seeded(logits, temperatures, top_k, top_p, seeds, positions) -> torc
     else:
         t = torch.from_numpy(host)
     return ops.sample_rows(logits, t[:3 * b].view(b, 3), t[4 * b:].view(torch.int64), t[3 * b:4 * b])
+
+
+# ------------------------------------------------------------------ per-token log-probabilities
+# A step in which some row asked for log-probabilities (``hb.logprobs`` is not None) answers with
+# one int32 tensor, the step's IDS MESSAGE, instead of its B ids:
+#     [ids B | chosen B (f32 bits) | top_ids B*N | top_lp B*N (f32 bits)],  N = max(hb.logprobs)
+# With N = 0 the two top sections are empty; rows that did not ask hold the kernel's filler.  A
+# step without an asking row sends its ids alone, as before.
+def _top_n(hb) -> int:
+    return max(0, int(hb.logprobs.max()))
+
+
+def ids_message_len(hb) -> int:
+    """int32 words the last stage answers a step with (both ends of a pipeline size by this)."""
+    b = hb.num_seqs
+    return b if hb.logprobs is None else b * (2 + 2 * _top_n(hb))
+
+
+def max_ids_message_len(max_batch: int) -> int:
+    """The longest ids message of a step of ``max_batch`` rows: every row asking for MAX_LOGPROBS
+    entries.  Transports with fixed ids slots (RcclTransport's ``max_ids``) are sized by it."""
+    return int(max_batch) * (2 + 2 * MAX_LOGPROBS)
+
+
+def pack_ids_message(ids, chosen, top_ids, top_lp) -> torch.Tensor:
+    return torch.cat([ids.to(torch.int32), chosen.view(torch.int32), top_ids.reshape(-1),
+                      top_lp.reshape(-1).view(torch.int32)])
+
+
+def unpack_ids_message(msg: np.ndarray, hb):
+    """-> (ids [B] int32, logprobs): ``logprobs`` is None for a step without an asking row, else
+    (chosen [B] float32, top_ids [B, N] int32, top_lp [B, N] float32), views of ``msg``."""
+    b = hb.num_seqs
+    msg = np.asarray(msg, dtype=np.int32)
+    if msg.shape[0] != ids_message_len(hb):
+        raise ValueError(f"ids message of {msg.shape[0]} words, expected {ids_message_len(hb)}")
+    if hb.logprobs is None:
+        return msg, None
+    n = _top_n(hb)
+    return msg[:b], (msg[b:2 * b].view(np.float32), msg[2 * b:(2 + n) * b].reshape(b, n),
+                     msg[(2 + n) * b:].view(np.float32).reshape(b, n))
+
+
+def sample_step(logits: torch.Tensor, hb):
+    """Sample a step's rows -> (ids [B] int32, message).  ``message`` is None unless a row of the
+    step asked for log-probabilities; then it is the ids message above: one more kernel
+    (``ops.token_logprobs``) over the logits the ids were drawn from."""
+    ids = sample(logits, **hb.sampling_args())
+    if hb.logprobs is None:
+        return ids, None
+    want = np.ascontiguousarray(hb.logprobs, dtype=np.int32)
+    want_t = _stage(want, logits.device) if logits.is_cuda else torch.from_numpy(want)
+    ids = ids.to(torch.int32)
+    return ids, pack_ids_message(ids, *ops.token_logprobs(logits, ids, want_t, _top_n(hb)))
 
 
 def step_sampling_args(seqs) -> dict:

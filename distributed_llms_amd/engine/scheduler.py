@@ -297,11 +297,27 @@ class Scheduler:
         return done
 
     # ------------------------------------------------------------ results
-    def complete(self, step: Step, tokens, now: Optional[float] = None) -> List[Sequence]:
-        """Apply sampled tokens of an executed step; returns sequences that finished."""
+    def _append_decode_logprobs(self, rows, logprobs) -> None:
+        """Log-probabilities of a step's decode rows, to the sequences that asked.  Runs BEFORE
+        native.complete retires the step's finishing sequences (they leave ``live`` there).  A row
+        whose id is no longer in ``live`` is a lookahead step's throw-away row (its sequence
+        finished by EOS one step earlier): skipped, like its token."""
+        chosen, top_ids, top_lp = logprobs
+        for i, sid in enumerate(rows):
+            seq = self.live.get(int(sid))
+            if seq is not None and seq.params.logprobs is not None:
+                n = seq.params.logprobs
+                seq.logprobs.append((float(chosen[i]), top_ids[i, :n].tolist(), top_lp[i, :n].tolist()))
+
+    def complete(self, step: Step, tokens, now: Optional[float] = None, logprobs=None) -> List[Sequence]:
+        """Apply sampled tokens of an executed step; returns sequences that finished.  ``logprobs``:
+        (chosen [B], top_ids [B, N], top_lp [B, N]) of the step's rows when one of them asked
+        (engine/sampler.py unpack_ids_message), else None."""
         now = time.perf_counter() if now is None else now
         if not step.is_prefill:
             toks = np.asarray(tokens, dtype=np.int32)
+            if logprobs is not None:
+                self._append_decode_logprobs(step.rows, logprobs)
             if self.native.complete(step.slot, step.rows, toks, now):
                 return self._sync_finished(now)
             return []
@@ -310,13 +326,16 @@ class Scheduler:
             # decode rows first in the batch: their tokens go to the native batcher
             toks = np.asarray(tokens, dtype=np.int32)
             nd = len(step.rows)
+            if logprobs is not None:
+                self._append_decode_logprobs(step.rows, logprobs)
+                logprobs = tuple(a[nd:] for a in logprobs)
             if self.native.complete(step.slot, step.rows, np.ascontiguousarray(toks[:nd]), now):
                 done.extend(self._sync_finished(now))
             tokens = toks[nd:]
         self.num_prefilling -= len(step.seqs)
         if hasattr(tokens, "tolist"):
             tokens = tokens.tolist()      # python ints once, not a numpy scalar per sequence
-        for seq, tok in zip(step.seqs, tokens):
+        for i, (seq, tok) in enumerate(zip(step.seqs, tokens)):
             st = seq.status
             if st is SeqStatus.FINISHED or st is SeqStatus.ABORTED:   # aborted while in flight
                 seq.chunk = 0
@@ -330,6 +349,10 @@ class Scheduler:
                 self.waiting.appendleft(seq)
                 continue
             seq.num_cached = len(seq.prompt) + len(seq.output)
+            if logprobs is not None and seq.params.logprobs is not None:
+                n = seq.params.logprobs
+                seq.logprobs.append((float(logprobs[0][i]), logprobs[1][i, :n].tolist(),
+                                     logprobs[2][i, :n].tolist()))
             if seq.append(tok, now) or seq.num_cached + 1 >= self.max_seq_len:
                 if not seq.finished:
                     seq.finish("max_seq_len", now)
@@ -341,7 +364,7 @@ class Scheduler:
             self.native.admit(step.slot, seq.seq_id, seq.total_len, seq.output[-1],
                               p.max_new_tokens - len(seq.output), _eos_of(seq),
                               int(round(p.temperature * 1e4)) if p.temperature > 0 else 0, int(p.top_k),
-                              int(round(p.top_p * 1e4)), *split_seed(seq.seed))
+                              int(round(p.top_p * 1e4)), *split_seed(seq.seed), seq.num_logprobs)
             self.live[seq.seq_id] = seq
         return done
 

@@ -29,6 +29,9 @@ class SamplingParams:
     top_p: float = 1.0
     ignore_eos: bool = False
     seed: Optional[int] = None
+    # per-token log-probabilities of the model's distribution: None = off, 0 = the chosen token's
+    # only, 1..MAX_LOGPROBS = that many most likely alternatives too (validate_logprobs)
+    logprobs: Optional[int] = None
 
     def to_dict(self):
         return dict(self.__dict__)
@@ -36,6 +39,19 @@ class SamplingParams:
     @staticmethod
     def from_dict(d):
         return SamplingParams(**{k: v for k, v in (d or {}).items() if k in SamplingParams.__dataclass_fields__})
+
+
+MAX_LOGPROBS = 20      # ops.MAX_LOGPROBS: the top slots of the kernel
+
+
+def validate_logprobs(value) -> Optional[int]:
+    """``SamplingParams.logprobs`` as the engines take it: None, or an int (not a bool) in
+    [0, MAX_LOGPROBS]; anything else raises ValueError."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= MAX_LOGPROBS:
+        raise ValueError(f"logprobs must be an integer from 0 to {MAX_LOGPROBS}, got {value!r}")
+    return value
 
 
 _ids = itertools.count(1)
@@ -80,11 +96,19 @@ class Sequence:
     # the 64-bit sampling seed of the request (request_seed), fixed at admission: preemption,
     # chunked prefill and recompute draw token n from Philox(seed, n) again
     seed: int = 0
+    # requests with params.logprobs set: one (chosen_lp, top_ids, top_lps) per generated token
+    logprobs: List[tuple] = field(default_factory=list)
 
     def __post_init__(self):
         if not self.prompt:
             raise ValueError("empty prompt")
         self.prompt = [int(t) for t in self.prompt]
+
+    @property
+    def num_logprobs(self) -> int:
+        """The row's ``HostBatch.logprobs`` word: -1 when the request did not ask."""
+        n = self.params.logprobs
+        return -1 if n is None else int(n)
 
     @property
     def total_len(self) -> int:

@@ -10,12 +10,18 @@ dependency; every request thread only submits to the master's request futures):
   GET  /metrics                Prometheus text: request metrics + per-worker gauges (HBM, KV blocks,
                                running / waiting sequences, microbatches executed)
   POST /generate               {"prompt": str | "prompt_ids": [int], "max_new_tokens", "temperature",
-                                "top_k", "top_p", "ignore_eos"} -> {"tokens", "text", "latency_s", ...}
+                                "top_k", "top_p", "ignore_eos", "logprobs"} -> {"tokens", "text",
+                                "latency_s", ...}; with "logprobs": n (0..20) also "logprobs":
+                                {"token_logprobs", "top_ids", "top_logprobs"}
   POST /v1/completions         OpenAI-style: {"prompt": str | [int] | [str...], "max_tokens", ...}
-                               -> {"object": "text_completion", "choices": [...], "usage": {...}}
+                               -> {"object": "text_completion", "choices": [...], "usage": {...}};
+                               "logprobs": n (0..20) adds to each choice the legacy object {"tokens",
+                               "token_logprobs", "top_logprobs": [{text: lp}], "text_offset"} plus
+                               "token_ids" / "top_token_ids" (two ids can decode to the same text);
+                               -inf is serialised as null
   "stream": true               (either POST, one prompt) server-sent events: one ``data: {...}`` event
                                per pipeline step that produced tokens (TOKENS messages from stage 0),
-                               then ``data: [DONE]``
+                               then ``data: [DONE]`` (not together with "logprobs": 400)
 
 Batches of prompts submitted together are scheduled together (continuous batching on stage 0).
 """
@@ -23,16 +29,18 @@ from __future__ import annotations
 
 import json
 import logging
+import math
 import threading
 import time
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from typing import Any, Dict, List, Tuple
 
+from ..engine.sequence import validate_logprobs
 from ..utils.metrics import cluster_prometheus_text
 
 log = logging.getLogger("dllm.http")
 
-_PARAM_KEYS = ("temperature", "top_k", "top_p", "ignore_eos", "seed")
+_PARAM_KEYS = ("temperature", "top_k", "top_p", "ignore_eos", "seed", "logprobs")
 
 
 def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_new_tokens") -> Dict[str, Any]:
@@ -40,7 +48,38 @@ def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_n
     p["max_new_tokens"] = int(body.get(max_key, body.get("max_new_tokens", default_max)))
     if p["max_new_tokens"] < 1:
         raise ValueError("max tokens must be >= 1")
+    validate_logprobs(p.get("logprobs"))
+    if p.get("logprobs") is not None and body.get("stream"):
+        raise ValueError("logprobs are not available with stream")
     return p
+
+
+def _finite(x: float):
+    """JSON has no -inf: a log-probability of -inf is serialised as null."""
+    return x if math.isfinite(x) else None
+
+
+def _generate_logprobs(lp: Dict[str, Any]) -> Dict[str, Any]:
+    return {"token_logprobs": [_finite(x) for x in lp["token_logprobs"]], "top_ids": lp["top_ids"],
+            "top_logprobs": [[_finite(x) for x in row] for row in lp["top_logprobs"]]}
+
+
+def _openai_logprobs(tokenizer, tokens: List[int], lp: Dict[str, Any]) -> Dict[str, Any]:
+    """The legacy OpenAI completions object, plus the ids (two ids can decode to the same text, and
+    then share a key of a ``top_logprobs`` dict: the more likely one, listed first, keeps it)."""
+    texts = [tokenizer.decode([t]) for t in tokens]
+    offsets, o = [], 0
+    for t in texts:
+        offsets.append(o)
+        o += len(t)
+    tops = []
+    for ids, lps in zip(lp["top_ids"], lp["top_logprobs"]):
+        d: Dict[str, Any] = {}
+        for i, x in zip(ids, lps):
+            d.setdefault(tokenizer.decode([i]), _finite(x))
+        tops.append(d)
+    return {"tokens": texts, "token_logprobs": [_finite(x) for x in lp["token_logprobs"]], "top_logprobs": tops,
+            "text_offset": offsets, "token_ids": list(tokens), "top_token_ids": lp["top_ids"]}
 
 
 class _Handler(BaseHTTPRequestHandler):
@@ -155,12 +194,17 @@ class _Handler(BaseHTTPRequestHandler):
         for f in futs:
             r = m._finish(f, self.timeout_s)
             r["text"] = m.tokenizer.decode(r["tokens"])
+            if r.get("logprobs") is None:
+                r.pop("logprobs", None)                # a request that did not ask: the reply it always got
             out.append(r)
         return out
 
     def _generate(self, body: Dict[str, Any]) -> Dict[str, Any]:
         ids = body["prompt_ids"] if "prompt_ids" in body else self._ids(body.get("prompt", ""))
-        return self._run([self._ids(ids)], _sampling(body))[0]
+        r = self._run([self._ids(ids)], _sampling(body))[0]
+        if "logprobs" in r:
+            r["logprobs"] = _generate_logprobs(r["logprobs"])
+        return r
 
     def _completions(self, body: Dict[str, Any]) -> Dict[str, Any]:
         prompt = body.get("prompt", "")
@@ -172,6 +216,9 @@ class _Handler(BaseHTTPRequestHandler):
         choices = [{"index": i, "text": r["text"], "tokens": r["tokens"],
                     "finish_reason": "length" if r.get("finish_reason") in ("length", "max_seq_len") else "stop"}
                    for i, r in enumerate(res)]
+        for c, r in zip(choices, res):
+            if "logprobs" in r:
+                c["logprobs"] = _openai_logprobs(self.master.tokenizer, r["tokens"], r["logprobs"])
         ptok = sum(len(p) for p in prompts)
         ctok = sum(len(r["tokens"]) for r in res)
         return {"id": res[0].get("task_id"), "object": "text_completion", "created": int(time.time()),

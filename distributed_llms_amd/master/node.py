@@ -32,7 +32,8 @@ import time
 from typing import Any, Dict, List, Optional, Sequence
 
 from ..config import EngineConfig, ModelConfig, get_model_config
-from ..network.protocol import MessageProtocol, pack_ids, unpack_ids
+from ..engine.sequence import validate_logprobs
+from ..network.protocol import MessageProtocol, pack_ids, unpack_ids, unpack_result
 from ..utils.metrics import RequestMetrics
 from ..utils.tokenizer import get_tokenizer
 
@@ -194,7 +195,8 @@ class MasterNode:
                 fut = self._tasks.pop(header.get("task_id"), None)
                 self._reqs.pop(header.get("task_id"), None)
             if fut and not fut.done():
-                fut.set_result((header, unpack_ids(payload)))
+                ids, lps = unpack_result(payload, header.get("num_tokens"), header.get("logprobs"))
+                fut.set_result((dict(header, logprobs=lps), ids))
             q = self._streams.get(header.get("task_id"))
             if q is not None:
                 q.put(None)                         # the stream's end: the full ids are in the future
@@ -530,6 +532,9 @@ class MasterNode:
         fut: cf.Future = cf.Future()
         fut.t_submit = time.perf_counter()
         ids, params = list(prompt_ids), dict(params or {})
+        validate_logprobs(params.get("logprobs"))      # a bad value fails here, not on the stage-0 worker
+        if params.get("logprobs") is not None and params.get("stream"):
+            raise ValueError("logprobs are not available with stream")
         with self._lock:
             # degraded with recovery on: hold the request with the parked in-flight ones (bounded)
             # until the stage is re-admitted (plan.md:430-436) -- checked under the
@@ -603,7 +608,7 @@ class MasterNode:
         lat = time.perf_counter() - fut.t_submit
         self.metrics.record(len(ids), lat, header.get("ttft_s"))
         return {"task_id": header.get("task_id"), "tokens": ids, "finish_reason": header.get("finish_reason"),
-                "latency_s": lat, "ttft_s": header.get("ttft_s")}
+                "latency_s": lat, "ttft_s": header.get("ttft_s"), "logprobs": header.get("logprobs")}
 
     def run_inference(self, input_text, timeout: float = 60, max_new_tokens: int = 32, **params) -> Dict[str, Any]:
         """Text (tokenized on the master) or token ids -> generated ids (+ detokenized text)."""

@@ -266,6 +266,40 @@ def unpack_ids(b: Optional[bytes]):
     return np.frombuffer(b, dtype=np.int32).tolist()
 
 
+def pack_result(ids, logprobs=None, num_logprobs: Optional[int] = None) -> bytes:
+    """A RESULT's binary payload: the T generated ids (int32) and, for a request that asked for
+    log-probabilities (``num_logprobs`` = n, not None), behind them
+    [chosen T f32 | top_ids T*n int32 | top_lp T*n f32] from ``logprobs``, the sequence's T entries
+    (chosen_lp, top_ids, top_lps).  The counts (T, n) travel in the message's metadata."""
+    import numpy as np
+    out = np.asarray(ids, dtype=np.int32).tobytes()
+    if num_logprobs is None:
+        return out
+    t, n = len(ids), int(num_logprobs)
+    if len(logprobs) != t:
+        raise ValueError(f"{len(logprobs)} logprob entries for {t} tokens")
+    chosen = np.array([e[0] for e in logprobs], dtype=np.float32)
+    top_ids = np.array([e[1] for e in logprobs], dtype=np.int32).reshape(t, n)
+    top_lp = np.array([e[2] for e in logprobs], dtype=np.float32).reshape(t, n)
+    return out + chosen.tobytes() + top_ids.tobytes() + top_lp.tobytes()
+
+
+def unpack_result(b: Optional[bytes], num_tokens: Optional[int] = None, num_logprobs: Optional[int] = None):
+    """-> (ids list, logprobs): ``logprobs`` is None unless ``num_logprobs`` is given, else
+    {"token_logprobs": [T floats], "top_ids": [T x n ints], "top_logprobs": [T x n floats]}."""
+    import numpy as np
+    if num_logprobs is None:
+        return unpack_ids(b), None
+    t, n = int(num_tokens), int(num_logprobs)
+    words = np.frombuffer(b or b"", dtype=np.int32)
+    if words.shape[0] != t * (2 + 2 * n):
+        raise ValueError(f"RESULT payload of {words.shape[0]} words for {t} tokens with {n} logprobs")
+    return words[:t].tolist(), {
+        "token_logprobs": words[t:2 * t].view(np.float32).tolist(),
+        "top_ids": words[2 * t:(2 + n) * t].reshape(t, n).tolist(),
+        "top_logprobs": words[(2 + n) * t:].view(np.float32).reshape(t, n).tolist()}
+
+
 def pack_tensors(tensors: Dict[str, "torch.Tensor"]) -> bytes:
     """Tensors -> safetensors bytes (no pickle on the wire)."""
     from safetensors.torch import save

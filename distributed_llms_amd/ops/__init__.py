@@ -24,7 +24,7 @@ __all__ = [
     "embedding", "rms_norm", "fused_add_rms_norm", "layer_norm", "linear", "silu_mul",
     "gelu_tanh", "rope_cache_append", "paged_attention_decode", "paged_attention_prefill",
     "argmax", "add_", "moe_route", "moe_mlp", "decode_split_plan", "paged_attention_decode_rope",
-    "paged_attention_prefill_rope", "sample_rows",
+    "paged_attention_prefill_rope", "sample_rows", "token_logprobs",
 ]
 
 
@@ -460,16 +460,16 @@ SAMPLE_MAX_VOCAB = 131072      # csrc/kernels/sampler.hip: 16 groups of 8 entrie
 _host_sampler_warned = False
 
 
-def _warn_host_sampler(logits: torch.Tensor) -> None:
+def _warn_host_sampler(logits: torch.Tensor, op: str = "sample_rows") -> None:
     """Once per process: GPU logits are about to be sampled by the host reference."""
     global _host_sampler_warned
     if not _host_sampler_warned:
         _host_sampler_warned = True
         import logging
         logging.getLogger("dllm.ops").warning(
-            "sample_rows: %s logits on %s take the host reference (knobs.fused_sampler=%s): the [B, V] logits are "
+            "%s: %s logits on %s take the host reference (knobs.fused_sampler=%s): the [B, V] logits are "
             "copied to the host every step, which synchronises the device and cannot be graph-captured",
-            logits.dtype, logits.device, knobs.K.fused_sampler)
+            op, logits.dtype, logits.device, knobs.K.fused_sampler)
 
 
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, seeds: torch.Tensor, pos: torch.Tensor,
@@ -507,6 +507,44 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, seeds: torch.Tensor,
                                seeds.data_ptr(), pos.data_ptr(), 0 if uniforms is None else uniforms.data_ptr(),
                                _stream())
     return out
+
+
+MAX_LOGPROBS = ref.MAX_LOGPROBS     # csrc/kernels/launchers.h kMaxLogprobs
+
+
+def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, n_max: int):
+    """Log-probabilities of the model's distribution (contract: ops/reference.py token_logprobs).
+
+    logits [B, V]; ids [B] int32 (the token each row chose); want [B] int32 (-1: the row is
+    skipped, else how many of the most likely entries to report, at most ``n_max`` <=
+    MAX_LOGPROBS) -> (chosen [B] float32, top_ids [B, n_max] int32, top_lp [B, n_max] float32).
+    Every per-row value is read on the device.  bf16 CUDA logits with a contiguous last dim of at
+    most SAMPLE_MAX_VOCAB entries take the HIP kernel; anything else, and everything with
+    ``knobs.fused_sampler`` off, the host reference (GPU logits: logged once, as sample_rows)."""
+    n_max = int(n_max)
+    if not 0 <= n_max <= MAX_LOGPROBS:
+        raise ValueError(f"token_logprobs: n_max must be in [0, {MAX_LOGPROBS}], got {n_max}")
+    if logits.dim() != 2:
+        raise ValueError("token_logprobs: logits must be [B, V]")
+    rows, v = logits.shape
+    _ck(ids, "token_logprobs.ids", torch.int32)
+    _ck(want, "token_logprobs.want", torch.int32)
+    if ids.shape != (rows,) or want.shape != (rows,):
+        raise ValueError(f"token_logprobs: ids / want must be [{rows}] / [{rows}]")
+    if ids.device != logits.device or want.device != logits.device:
+        raise ValueError("token_logprobs: ids and want must be on the logits' device")
+    if not (_gpu(logits) and logits.dtype == torch.bfloat16 and logits.stride(-1) == 1 and knobs.K.fused_sampler
+            and v <= SAMPLE_MAX_VOCAB):
+        if _gpu(logits):
+            _warn_host_sampler(logits, "token_logprobs")
+        return ref.token_logprobs(logits, ids, want, n_max)
+    dev = logits.device
+    chosen = torch.empty(rows, dtype=torch.float32, device=dev)
+    top_ids = torch.empty(rows, n_max, dtype=torch.int32, device=dev)
+    top_lp = torch.empty(rows, n_max, dtype=torch.float32, device=dev)
+    _ext.kernels().token_logprobs(chosen.data_ptr(), top_ids.data_ptr(), top_lp.data_ptr(), logits.data_ptr(), rows, v,
+                                  logits.stride(0), ids.data_ptr(), want.data_ptr(), n_max, _stream())
+    return chosen, top_ids, top_lp
 
 
 # ------------------------------------------------------------ K11/K12

@@ -340,6 +340,64 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, seeds: torch.Tensor,
     return torch.from_numpy(ids).to(logits.device)
 
 
+# ------------------------------------------------------------------ per-token log-probabilities
+# The contract of token_logprobs_kernel (csrc/kernels/sampler.hip), in numpy float64: the
+# log-probabilities of the model's distribution (temperature, top-k and top-p play no part).
+#   NaN counts as -inf and -0 equals +0 (the sampler's key order); m = row maximum;
+#   Z = sum_j exp(x_j - m), an entry equal to m contributing exactly 1;
+#   lp_i = (x_i - m) - ln Z with x_i - m = 0 where x_i == m; a row whose maximum is -inf has every
+#   lp = -inf; a +inf maximum falls out: the +inf entries get -ln(count), the rest -inf.
+#   want[b] < 0   the row is skipped: chosen = 0, top_ids = -1, top_lp = 0
+#   want[b] = n   chosen = lp[ids[b]] (-inf, nothing read, for an id outside [0, V)); the first
+#                 min(n, n_max, V) top slots hold the largest entries by decreasing value, then
+#                 increasing index; the remaining slots hold -1 / 0
+MAX_LOGPROBS = 20
+
+
+def token_logprobs_detail(logits, ids, want, n_max: int):
+    """The contract on numpy arrays: logits [B, V] floats, ids [B] and want [B] ints ->
+    (chosen float64 [B], top_ids int32 [B, n_max], top_lp float64 [B, n_max])."""
+    import numpy as np
+    l = np.array(logits, dtype=np.float64)
+    b, v = l.shape
+    ids = np.asarray(ids, dtype=np.int64).reshape(b)
+    want = np.asarray(want, dtype=np.int64).reshape(b)
+    chosen = np.zeros(b, dtype=np.float64)
+    top_ids = np.full((b, n_max), -1, dtype=np.int32)
+    top_lp = np.zeros((b, n_max), dtype=np.float64)
+    l[np.isnan(l)] = -np.inf
+    for r in range(b):
+        if want[r] < 0:
+            continue
+        x = l[r]
+        m = x.max()
+        if np.isneginf(m):
+            lp = np.full(v, -np.inf)
+        else:
+            with np.errstate(invalid="ignore"):
+                d = x - m
+            d[x == m] = 0.0                      # inf - inf at a +inf maximum
+            lp = d - np.log(np.exp(d).sum())
+        chosen[r] = lp[ids[r]] if 0 <= ids[r] < v else -np.inf
+        n = int(min(want[r], n_max, v))
+        if n > 0:
+            order = np.argsort(-x, kind="stable")[:n]     # -0 == +0: ties fall to the smaller index
+            top_ids[r, :n] = order
+            top_lp[r, :n] = lp[order]
+    return chosen, top_ids, top_lp
+
+
+def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, n_max: int):
+    """logits [B, V]; ids [B] int32 (the chosen tokens); want [B] int32 (-1: skip the row, else how
+    many top entries) -> (chosen [B] float32, top_ids [B, n_max] int32, top_lp [B, n_max] float32)
+    on the logits' device."""
+    lg = logits.detach().to(torch.float64).cpu().numpy()
+    c, ti, tl = token_logprobs_detail(lg, ids.detach().cpu().numpy(), want.detach().cpu().numpy(), int(n_max))
+    dev = logits.device
+    return (torch.from_numpy(c).to(torch.float32).to(dev), torch.from_numpy(ti).to(dev),
+            torch.from_numpy(tl).to(torch.float32).to(dev))
+
+
 def moe_route(router_logits: torch.Tensor, top_k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Mixtral routing: softmax over experts, top-k, renormalise. -> (weights f32, ids i32)."""
     probs = torch.softmax(router_logits.float(), dim=-1)

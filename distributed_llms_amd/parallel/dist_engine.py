@@ -18,6 +18,7 @@ import torch.distributed as dist
 from ..config import EngineConfig
 from ..engine.llm_engine import LLMEngine, build_stage, make_block_manager
 from ..engine.runner import StageRunner, plan_kv_blocks
+from ..engine.sampler import max_ids_message_len
 from .comm import DistTransport
 from .pipeline import PipelineDriver, inflight_window, stage_worker_loop
 from .planner import plan_units
@@ -155,12 +156,13 @@ def resolve_transport(kind: str, device: str, host_staged: bool) -> str:
 
 
 def make_transport(ranks, stage: int, ctrl_group, data_group, device: str, ring_group=None, hop=None,
-                   kind: str = "auto", timeout_s: float = 600.0):
+                   kind: str = "auto", timeout_s: float = 600.0, max_ids: int = 0):
     """Activation transport for one pipeline stage (see resolve_transport).  ``hop`` = (max rows,
     hidden, dtype, in-flight window) of an activation hop: every GPU transport sizes its static
     rings from it.  If the native RCCL communicators cannot be created on some rank, EVERY rank of
     the job falls back to torch.distributed's RCCL group (agreed over the control group), so a
-    library or topology problem costs speed, not the run."""
+    library or topology problem costs speed, not the run.  ``max_ids``: int32 words of the longest
+    ids message a step answers with (the RCCL transport's ids ring slots; 0: the hop's rows)."""
     kind = resolve_transport(kind, device, data_group is not None)
     on_gpu = str(device).startswith("cuda")
     from . import rccl_standin
@@ -175,7 +177,7 @@ def make_transport(ranks, stage: int, ctrl_group, data_group, device: str, ring_
         t, err = None, None
         try:
             t = RcclTransport(ranks, stage, ctrl_group, device, rows, hidden, dtype, ring_group=ring_group,
-                              window=window, timeout_s=timeout_s)
+                              window=window, timeout_s=timeout_s, max_ids=max(int(max_ids), rows))
         except Exception as e:          # noqa: BLE001 - reported, then the whole job agrees on a fallback
             err = e
         ok = torch.tensor([0 if err is None else 1], dtype=torch.int64)
@@ -239,7 +241,8 @@ class RankRole:
                    inflight_window(ecfg, ctx.pp, stage.device))
             self.transport = make_transport(ctx.pipeline_ranks, ctx.stage, ctx.ctrl_group, ctx.data_group,
                                             ctx.device, ctx.ring_group, hop=hop, kind=ecfg.transport,
-                                            timeout_s=ecfg.comm_timeout_s)
+                                            timeout_s=ecfg.comm_timeout_s,
+                                            max_ids=max_ids_message_len(ecfg.max_batch))
             if ctx.stage == 0 and ctx.tp_rank == 0:
                 bm = make_block_manager(nb, ecfg.kv_block_size)
                 self.driver = PipelineDriver(self.runner, self.transport, ecfg, bm)

@@ -35,9 +35,9 @@ from .. import knobs
 from ..config import EngineConfig, pipeline_slots, resolve_device  # noqa: F401  (pipeline_slots re-exported)
 from ..engine.batch import HostBatch, build_host_batch
 from ..engine.runner import StageRunner
-from ..engine.sampler import sample
+from ..engine.sampler import ids_message_len, sample_step, unpack_ids_message
 from ..engine.scheduler import Scheduler, Step
-from ..engine.sequence import SamplingParams, Sequence, request_seed
+from ..engine.sequence import SamplingParams, Sequence, request_seed, validate_logprobs
 from ..utils.tracing import get_tracer
 from .comm import STOP, PendingIds, Transport
 
@@ -79,7 +79,9 @@ def stage_worker_loop(runner: StageRunner, transport: Transport, stop_on_round_e
                 from .tensor_parallel import tp_sample
                 transport.send_ids(tp_sample(out, st.tp, hb.sampling_args()))
             else:
-                transport.send_ids(sample(out, **hb.sampling_args()))
+                # a step in which a row asked for log-probabilities answers with its ids message
+                ids, msg = sample_step(out, hb)
+                transport.send_ids(ids if msg is None else msg)
         else:
             with tr.span("pp.send_hidden", cat="comm", step=hb.step_id):
                 transport.send_hidden(out)
@@ -87,10 +89,11 @@ def stage_worker_loop(runner: StageRunner, transport: Transport, stop_on_round_e
 
 class _Issued:
     """A microbatch stage 0 has issued and not yet completed on the host."""
-    __slots__ = ("step", "sid", "ids")
+    __slots__ = ("step", "sid", "ids", "hb")
 
-    def __init__(self, step: Step, sid: int, ids: PendingIds):
-        self.step, self.sid, self.ids = step, sid, ids
+    def __init__(self, step: Step, sid: int, ids: PendingIds, hb: HostBatch):
+        # ids: the step's ids message (engine/sampler.py): its first step.size words are the ids
+        self.step, self.sid, self.ids, self.hb = step, sid, ids, hb
 
 
 def inflight_window(ecfg: EngineConfig, pp: int, device=None) -> int:
@@ -128,8 +131,10 @@ class PipelineDriver:
 
     def add_request(self, prompt: List[int], params: Optional[SamplingParams] = None,
                     request_id: Optional[str] = None) -> Sequence:
-        seq = Sequence(list(prompt), params or SamplingParams(), eos_token_id=self.mcfg.eos_token_id,
-                       request_id=request_id)
+        params = params or SamplingParams()
+        if validate_logprobs(params.logprobs) is not None and self.tp is not None:
+            raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
+        seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id)
         seq.seed = request_seed(seq.params, self._seed_rng)
         self.scheduler.add(seq)
         return seq
@@ -144,7 +149,7 @@ class PipelineDriver:
         out = self.runner.execute(hb, ids_dev=ids_dev) if ids_dev is not None else self.runner.execute(hb)
         self.t.send_hidden(out)
         # the ids receive is posted right away: receives are matched in issue order
-        it = _Issued(step, self.step_id, self.t.recv_ids(step.size, self.device))
+        it = _Issued(step, self.step_id, self.t.recv_ids(ids_message_len(hb), self.device), hb)
         self.inflight.append(it)
         self.per_slot[step.slot].append(it)
         self.step_id += 1
@@ -159,9 +164,13 @@ class PipelineDriver:
         with get_tracer().span("pp.wait_tokens", cat="comm", step=it.sid):
             toks = it.ids.host()
         self.stall_s += time.perf_counter() - t0
-        if toks.shape[0] != it.step.size:
-            raise RuntimeError(f"pipeline out of order: step {it.sid} got {toks.shape[0]} ids for {it.step.size} rows")
-        return self.scheduler.complete(it.step, toks, time.perf_counter())
+        if toks.shape[0] != ids_message_len(it.hb):
+            raise RuntimeError(f"pipeline out of order: step {it.sid} got {toks.shape[0]} words for {it.step.size} "
+                               f"rows ({ids_message_len(it.hb)} expected)")
+        if it.hb.logprobs is None:
+            return self.scheduler.complete(it.step, toks, time.perf_counter())
+        toks, lps = unpack_ids_message(toks, it.hb)
+        return self.scheduler.complete(it.step, toks, time.perf_counter(), lps)
 
     def _issue_lookahead(self, slot: int) -> bool:
         """The slot's next decode step on the device ids of its in-flight step (see module doc)."""
@@ -173,7 +182,7 @@ class PipelineDriver:
         step = self.scheduler.schedule_lookahead(slot)
         if step is None:
             return False
-        prev = q[0].ids.wait()                   # stream-ordered behind the ids' arrival
+        prev = q[0].ids.wait()[:q[0].step.size]  # stream-ordered behind the ids' arrival
         if step.keep is not None:
             keep = torch.from_numpy(np.asarray(step.keep, dtype=np.int64))
             prev = prev.index_select(0, keep.to(prev.device, non_blocking=True) if prev.is_cuda else keep)

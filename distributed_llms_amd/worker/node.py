@@ -31,7 +31,8 @@ import torch
 from ..config import EngineConfig, ModelConfig, get_model_config, resolve_device
 from ..models import weights as W
 from ..models.stage import BatchMeta, ModelStage
-from ..network.protocol import MessageProtocol, pack_ids, pack_tensors, unpack_ids, unpack_tensors
+from ..network.protocol import (MessageProtocol, pack_ids, pack_result, pack_tensors, unpack_ids,
+                                unpack_tensors)
 
 log = logging.getLogger("dllm.worker")
 
@@ -444,6 +445,7 @@ class WorkerNode:
         else:
             self.stage_runner = StageRunner(stage, ecfg, num_blocks=nb)
             from ..parallel.dist_engine import make_transport
+            from ..engine.sampler import max_ids_message_len
             from ..parallel.pipeline import inflight_window
             # hop slots fit the widest hop of the plan: a sub-layer cut (group != 2) also carries the
             # pending tensor next to the hidden state (as parallel/dist_engine.py sizes it)
@@ -453,7 +455,8 @@ class WorkerNode:
                                        ctx.ring_group,
                                        hop=(max(ecfg.max_prefill_tokens, ecfg.max_batch), width,
                                             stage.dtype, inflight_window(ecfg, world, stage.device)),
-                                       kind=ecfg.transport, timeout_s=ecfg.comm_timeout_s)
+                                       kind=ecfg.transport, timeout_s=ecfg.comm_timeout_s,
+                                       max_ids=max_ids_message_len(ecfg.max_batch))
             self._transport = transport
             if stage_idx == 0:
                 bm = make_block_manager(nb, ecfg.kv_block_size)
@@ -571,7 +574,11 @@ class WorkerNode:
                     continue
                 meta = {"task_id": s.request_id, "finish_reason": s.finish_reason, "num_tokens": len(s.output),
                         "ttft_s": s.ttft(), "latency_s": s.latency(), "prompt_tokens": len(s.prompt)}
-                self.proto.send_message(sock, "RESULT", payload=pack_ids(s.output), metadata=meta)
+                n_lp = s.params.logprobs
+                if n_lp is not None:      # the values ride in the payload behind the ids; the count here
+                    meta["logprobs"] = n_lp
+                self.proto.send_message(sock, "RESULT", payload=pack_result(s.output, s.logprobs, n_lp),
+                                        metadata=meta)
 
     def _teardown_pipeline(self, send_stop: bool):
         if self.driver is not None and send_stop:

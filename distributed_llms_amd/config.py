@@ -248,6 +248,10 @@ class EngineConfig:
     # the full prefill rate and latency-bound deployments lower it (profiles/round5_open_loop.md)
     mixed_prefill_tokens: int = 8192
     max_seq_len: int = 4096
+    # LogitState rows (engine/logit_state.py): requests with logit processors that can be admitted
+    # at once, 4 bytes x vocabulary each on the sampling stage, allocated when the first one arrives.
+    # 0 -> slots x (per-slot batch + 2): every decode row asking, plus the rows in quarantine
+    logit_state_rows: int = 0
     kv_block_size: int = 32            # tokens per paged-KV block
     kv_cache_fraction: float = 0.80    # of free HBM after weights
     num_kv_blocks: int = 0             # 0 -> derive from kv_cache_fraction
@@ -291,6 +295,10 @@ class EngineConfig:
             raise ValueError(f"unknown kernel_knobs {sorted(unknown)}")
         if self.max_batch < 1 or self.max_seq_len < 2:
             raise ValueError("max_batch/max_seq_len")
+        if self.max_seq_len >= 1 << 24:
+            raise ValueError("max_seq_len must be below 2^24 (the logit processors count outputs in 24 bits)")
+        if self.logit_state_rows < 0:
+            raise ValueError("logit_state_rows must be >= 0")
         cfg = get_model_config(self.model if self.shard_dir is None else self.shard_dir)
         if self.num_workers > cfg.num_layers:
             raise ValueError(f"{self.num_workers} stages > {cfg.num_layers} layers")

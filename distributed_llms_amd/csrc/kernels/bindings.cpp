@@ -20,6 +20,10 @@ PYBIND11_MODULE(_C_kernels, m) {
   m.def("sample_rows", &dllm::sample_rows);
   m.def("token_logprobs", &dllm::token_logprobs);
   m.attr("MAX_LOGPROBS") = dllm::kMaxLogprobs;
+  m.def("apply_logit_processors", &dllm::apply_logit_processors);
+  m.def("logit_state_update", &dllm::logit_state_update);
+  m.def("logit_state_count", &dllm::logit_state_count);
+  m.attr("PROC_WORDS") = dllm::kProcWords;
   m.def("add_inplace", &dllm::add_inplace);
   m.def("moe_route", &dllm::moe_route);
   m.def("moe_grouped_gemm", &dllm::moe_grouped_gemm);

@@ -30,6 +30,20 @@ void sample_rows(uintptr_t out_ids, uintptr_t logits, int rows, int vocab, long 
 constexpr int kMaxLogprobs = 20;
 void token_logprobs(uintptr_t chosen, uintptr_t top_ids, uintptr_t top_lp, uintptr_t logits, int rows, int vocab,
                     long row_stride, uintptr_t ids, uintptr_t want, int n_max, uintptr_t stream);
+// logit_processors.hip: penalties, logit_bias and the min_tokens EOS ban on the bf16 logits, in place.  state
+// [state_rows, pitch] u32 (one row per asking request), procs [rows, kProcWords] i32 (the layout is in the file's
+// head), bias_n [state_rows] i32, bias_ids / bias_vals [state_rows, bias_pitch]; step_bias_* the lists a step installs
+// (cu [rows + 1]); all on the device
+constexpr int kProcWords = 8;
+void apply_logit_processors(uintptr_t logits, int rows, int vocab, long row_stride, uintptr_t state, int pitch,
+                            int state_rows, uintptr_t procs, uintptr_t seq_lens, int eos_id, uintptr_t bias_n,
+                            uintptr_t bias_ids, uintptr_t bias_vals, int bias_pitch, uintptr_t stream);
+void logit_state_update(uintptr_t state, int pitch, int state_rows, int vocab, uintptr_t ids, uintptr_t cu_seqlens,
+                        uintptr_t procs, int rows, uintptr_t bias_n, uintptr_t bias_ids, uintptr_t bias_vals,
+                        int bias_pitch, uintptr_t step_bias_cu, uintptr_t step_bias_ids, uintptr_t step_bias_vals,
+                        uintptr_t stream);
+void logit_state_count(uintptr_t state, int pitch, int state_rows, int vocab, uintptr_t ids, uintptr_t procs, int rows,
+                       uintptr_t stream);
 
 void splitk_add_rms_norm(uintptr_t y, uintptr_t residual, uintptr_t ws, int S, int M, int N, uintptr_t w, float eps,
                          uintptr_t stream);

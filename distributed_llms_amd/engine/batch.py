@@ -14,6 +14,7 @@ import torch
 
 from ..models.stage import BatchMeta
 from .scheduler import Step
+from ..ops.reference import PROC_FREQ, PROC_PRES, PROC_REP, PROC_ROW, PROC_SAMPLE, PROC_UPDATE, PROC_WORDS
 from .sequence import split_seed
 
 _FIELDS = ("ids", "positions", "slots", "seq_lens", "cu_seqlens", "block_tables", "logits_idx")
@@ -47,6 +48,18 @@ class HostBatch:
     # chosen token's only, -1: the row did not ask); None when no row asks -- the packed array is
     # then what it was without the field.  Packed after ``sample_seeds`` with header word 11 set
     logprobs: Optional[np.ndarray] = None
+    # logit processors (ops/reference.py): None when no row of the step asks -- the packed array is
+    # then what it was without the fields, and no processor kernel runs.  Else ``procs`` [B,
+    # PROC_WORDS] int32, one record per row (state row or -1, prompt length, PROC_SAMPLE /
+    # PROC_UPDATE flags, the three penalties as float32 bits, min_tokens, chunk start), the bias
+    # lists of the rows whose chunk starts at position 0 (``bias_cu`` [B + 1], ``bias_ids`` and
+    # ``bias_vals`` (float32 bits) [n]) and ``state_rows``, the row count of every stage's
+    # LogitState.  Packed after ``logprobs`` with header word 12 set
+    procs: Optional[np.ndarray] = None
+    bias_cu: Optional[np.ndarray] = None
+    bias_ids: Optional[np.ndarray] = None
+    bias_vals: Optional[np.ndarray] = None
+    state_rows: int = 0
 
     @property
     def num_tokens(self) -> int:
@@ -68,8 +81,9 @@ class HostBatch:
         has_s = 1 if self.sampling is not None else 0
         has_seeds = 1 if self.sample_seeds is not None else 0
         has_lp = 1 if self.logprobs is not None else 0
+        has_pr = 1 if self.procs is not None else 0
         hdr = np.array([1 if self.is_prefill else 0, t, b, mb, self.max_q_len, self.max_ctx, self.slot,
-                        self.step_id, has_s, self.num_decode, has_seeds, has_lp] + [0] * 4, dtype=np.int32)
+                        self.step_id, has_s, self.num_decode, has_seeds, has_lp, has_pr] + [0] * 3, dtype=np.int32)
         parts = [hdr, self.ids, self.positions, self.slots, self.seq_lens, self.cu_seqlens,
                  self.block_tables.reshape(-1), self.logits_idx]
         if has_s:
@@ -78,6 +92,9 @@ class HostBatch:
             parts.append(self.sample_seeds.reshape(-1))
         if has_lp:
             parts.append(self.logprobs)
+        if has_pr:
+            parts += [np.array([self.state_rows], dtype=np.int32), self.procs.reshape(-1), self.bias_cu,
+                      self.bias_ids, self.bias_vals]
         return np.concatenate([p.astype(np.int32, copy=False).reshape(-1) for p in parts])
 
     def sampling_args(self) -> dict:
@@ -109,8 +126,48 @@ class HostBatch:
         samp = take(3 * b).reshape(b, 3) if has_s else None
         seeds = take(2 * b).reshape(b, 2) if int(hdr[10]) else None
         lps = take(b) if int(hdr[11]) else None
-        return HostBatch(bool(pf), ids, pos, slots, seq_lens, cu, bt, lidx, mq, mc, slot, sid, samp, raw=arr,
-                         num_decode=nd, sample_seeds=seeds, logprobs=lps)
+        hb = HostBatch(bool(pf), ids, pos, slots, seq_lens, cu, bt, lidx, mq, mc, slot, sid, samp, raw=arr,
+                       num_decode=nd, sample_seeds=seeds, logprobs=lps)
+        if int(hdr[12]):
+            hb.state_rows = int(take(1)[0])
+            hb.procs, hb.bias_cu = take(PROC_WORDS * b).reshape(b, PROC_WORDS), take(b + 1)
+            nb = int(hb.bias_cu[-1])
+            hb.bias_ids, hb.bias_vals = take(nb), take(nb)
+        return hb
+
+
+def _f32_bits(values) -> np.ndarray:
+    return np.asarray(values, dtype=np.float32).view(np.int32)
+
+
+def attach_procs(hb: HostBatch, seqs, state_rows: int, prefill: bool) -> None:
+    """Give ``hb`` its processors section when a row of it asks (a sequence with processors holds a
+    LogitState row, ``seq.state_row``).  ``seqs``: the batch's sequences in row order, all decode
+    rows or all prefill chunks (a mixed step merges one of each).  Decode rows and final chunks
+    carry PROC_SAMPLE, chunks PROC_UPDATE; a chunk that starts at position 0 brings its bias list."""
+    if not any(s.state_row >= 0 for s in seqs):
+        return
+    b = len(seqs)
+    procs = np.zeros((b, PROC_WORDS), dtype=np.int32)
+    procs[:, PROC_ROW] = -1
+    cu = np.zeros(b + 1, dtype=np.int32)
+    bids, bvals = [], []
+    for i, s in enumerate(seqs):
+        if s.state_row >= 0:
+            p = s.params
+            start = s.num_cached if prefill else 0
+            flags = (PROC_UPDATE | (0 if s.chunk else PROC_SAMPLE)) if prefill else PROC_SAMPLE
+            procs[i] = (s.state_row, len(s.prompt), flags, 0, 0, 0, p.min_tokens, start)
+            procs[i, [PROC_REP, PROC_PRES, PROC_FREQ]] = _f32_bits(
+                [p.repetition_penalty, p.presence_penalty, p.frequency_penalty])
+            if prefill and start == 0 and p.logit_bias:
+                bids.extend(p.logit_bias.keys())
+                bvals.extend(p.logit_bias.values())
+        cu[i + 1] = len(bids)
+    hb.procs, hb.bias_cu, hb.state_rows = procs, cu, int(state_rows)
+    hb.bias_ids = np.asarray(bids, dtype=np.int32).reshape(-1)
+    hb.bias_vals = _f32_bits(bvals).reshape(-1)
+    hb.raw = None            # a natively packed batch: pack() concatenates again, section included
 
 
 def next_pow2(x: int, lo: int = 1) -> int:
@@ -125,13 +182,19 @@ def build_host_batch(step: Step, bm, block_size: int, max_blocks: Optional[int] 
     """Metadata of one step.  Decode steps of the native batcher arrive packed already (their
     block-table width is the scheduler's ``max_blocks``); only the step id is stamped here.  A
     mixed step is the decode rows' packed batch followed by its prefill chunk's (merge_mixed)."""
+    state_rows = getattr(step, "state_rows", 0)
     if getattr(step, "mixed", False):
         dec = HostBatch.unpack(step.packed)
-        pre = build_host_batch(Step(True, step.seqs, step.slot), bm, block_size, None, step_id)
+        if state_rows:
+            attach_procs(dec, step.decode_seqs, state_rows, False)
+        pre = build_host_batch(Step(True, step.seqs, step.slot, state_rows=state_rows), bm, block_size, None, step_id)
         return merge_mixed(dec, pre, step.slot, step_id)
     if step.packed is not None:
         step.packed[7] = step_id
-        return HostBatch.unpack(step.packed)
+        hb = HostBatch.unpack(step.packed)
+        if state_rows:
+            attach_procs(hb, step.seqs, state_rows, False)
+        return hb
     seqs = step.seqs
     b = len(seqs)
     seq_ids = np.fromiter((s.seq_id for s in seqs), dtype=np.int64, count=b)
@@ -181,8 +244,11 @@ def build_host_batch(step: Step, bm, block_size: int, max_blocks: Optional[int] 
     lps = None
     if any(s.params.logprobs is not None for s in seqs):
         lps = np.fromiter((s.num_logprobs for s in seqs), dtype=np.int32, count=b)
-    return HostBatch(step.is_prefill, ids, positions, slots, seq_lens, cu, bt, logits_idx, max_q_len,
-                     max_ctx, step.slot, step_id, sampling, sample_seeds=seeds, logprobs=lps)
+    hb = HostBatch(step.is_prefill, ids, positions, slots, seq_lens, cu, bt, logits_idx, max_q_len,
+                   max_ctx, step.slot, step_id, sampling, sample_seeds=seeds, logprobs=lps)
+    if state_rows:
+        attach_procs(hb, seqs, state_rows, step.is_prefill)
+    return hb
 
 
 def merge_mixed(dec: HostBatch, pre: HostBatch, slot: int, step_id: int) -> HostBatch:
@@ -211,13 +277,27 @@ def merge_mixed(dec: HostBatch, pre: HostBatch, slot: int, step_id: int) -> Host
         lps = np.concatenate([dec.logprobs if dec.logprobs is not None else np.full(nd, -1, np.int32),
                               pre.logprobs if pre.logprobs is not None
                               else np.full(pre.num_seqs, -1, np.int32)]).astype(np.int32)
-    return HostBatch(True, np.concatenate([dec.ids, pre.ids]).astype(np.int32),
+    hb = HostBatch(True, np.concatenate([dec.ids, pre.ids]).astype(np.int32),
                      np.concatenate([dec.positions, pre.positions]).astype(np.int32),
                      np.concatenate([dec.slots, pre.slots]).astype(np.int32),
                      np.concatenate([dec.seq_lens, pre.seq_lens]).astype(np.int32), cu, bt,
                      np.concatenate([np.arange(nd, dtype=np.int32), pre.logits_idx.astype(np.int32) + nd]),
                      max(1, pre.max_q_len), max(dec.max_ctx, pre.max_ctx), slot, step_id, sampling, num_decode=nd,
                      sample_seeds=seeds, logprobs=lps)
+    if dec.procs is not None or pre.procs is not None:
+        def none(n):
+            p = np.zeros((n, PROC_WORDS), dtype=np.int32)
+            p[:, PROC_ROW] = -1
+            return p
+        hb.procs = np.concatenate([dec.procs if dec.procs is not None else none(nd),
+                                   pre.procs if pre.procs is not None else none(pre.num_seqs)]).astype(np.int32)
+        # decode rows install no bias list: the chunks' offsets follow nd empty lists
+        pcu = pre.bias_cu if pre.procs is not None else np.zeros(pre.num_seqs + 1, np.int32)
+        hb.bias_cu = np.concatenate([np.zeros(nd, np.int32), pcu]).astype(np.int32)
+        hb.bias_ids = pre.bias_ids if pre.procs is not None else np.zeros(0, np.int32)
+        hb.bias_vals = pre.bias_vals if pre.procs is not None else np.zeros(0, np.int32)
+        hb.state_rows = max(dec.state_rows, pre.state_rows)
+    return hb
 
 
 def build_decode_batch(seq_ids: np.ndarray, seq_lens: np.ndarray, bm, block_size: int, max_blocks: int,

@@ -25,7 +25,8 @@ from .graphs import SCRATCH_SEQ_ID
 from .runner import StageRunner
 from .sampler import ids_message_len, max_ids_message_len, sample_step, unpack_ids_message
 from .scheduler import Scheduler, Step
-from .sequence import SamplingParams, Sequence, request_seed, validate_logprobs
+from .logit_state import LogitState
+from .sequence import SamplingParams, Sequence, request_seed, validate_logprobs, validate_processors
 
 log = logging.getLogger("dllm.engine")
 
@@ -76,7 +77,8 @@ class LLMEngine:
         # max_batch is the engine's total decode batch, split evenly over the slots
         per_slot = -(-ecfg.max_batch // self.num_slots)
         self.scheduler = Scheduler(self.bm, self.num_slots, per_slot, ecfg.max_prefill_tokens, ecfg.max_seq_len,
-                                   ecfg.mixed_prefill_tokens)
+                                   ecfg.mixed_prefill_tokens, ecfg.logit_state_rows)
+        self.logit_state = LogitState()      # device memory only once a request asks for logit processors
         self._seed_rng = random.Random(os.urandom(16))     # seeds of sampled requests that bring none
         self.step_id = 0
         self.num_prefill_tokens = 0
@@ -107,6 +109,9 @@ class LLMEngine:
             # the tensor-parallel lanes draw with a distributed arg-max over vocabulary shards;
             # log-probabilities there need a distributed log-sum-exp
             raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
+        if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
+            # the processors rewrite whole logit rows; the tensor-parallel lanes hold vocabulary shards
+            raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
         seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id)
         seq.seed = request_seed(seq.params, self._seed_rng)
         self.scheduler.add(seq)
@@ -147,7 +152,7 @@ class LLMEngine:
         if self.tp is not None:
             from ..parallel.tensor_parallel import tp_sample
             return tp_sample(logits, self.tp, hb.sampling_args()), None
-        return sample_step(logits, hb)
+        return sample_step(logits, hb, self.logit_state, self.mcfg.eos_token_id)
 
     def _launch(self, step: Step, hb, slot: int, ids_src: Optional[torch.Tensor] = None, keep=None):
         """``ids_src`` (lookahead): the in-flight step's sampled ids on the device, rows ``keep``

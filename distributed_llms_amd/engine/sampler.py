@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .logit_state import stage_section
 from .sequence import MAX_LOGPROBS, split_seed
 
 
@@ -52,7 +53,8 @@ def sample(logits: torch.Tensor, temperatures: Optional[Seq[float]] = None, top_
 
 
 # pinned buffers per device: more than the uploads of the steps one slot keeps in flight (a step
-# makes up to two: the sampler's parameters and, when a row asks, the logprobs counts)
+# makes up to three: the sampler's parameters and, when a row asks, the logprobs counts and the
+# processors section)
 _STAGE_DEPTH = 8
 _stages: dict = {}
 
@@ -140,11 +142,30 @@ def unpack_ids_message(msg: np.ndarray, hb):
                      msg[(2 + n) * b:].view(np.float32).reshape(b, n))
 
 
-def sample_step(logits: torch.Tensor, hb):
+def sample_step(logits: torch.Tensor, hb, state=None, eos_id: Optional[int] = None):
     """Sample a step's rows -> (ids [B] int32, message).  ``message`` is None unless a row of the
     step asked for log-probabilities; then it is the ids message above: one more kernel
-    (``ops.token_logprobs``) over the logits the ids were drawn from."""
+    (``ops.token_logprobs``) over the logits the ids were drawn from.
+
+    A step with a processors section (``hb.procs``; ``state``: the caller's LogitState, ``eos_id``
+    the id min_tokens bans) first brings the state rows of its prefill chunks up to date, then
+    rewrites the asking rows of ``logits`` in place -- what argmax, the sampler and the
+    log-probabilities then see -- and afterwards counts the ids those rows drew."""
+    sec = None
+    if hb.procs is not None:
+        if state is None:
+            raise ValueError("sample_step: the step carries logit processors but no LogitState was given")
+        state.ensure(hb.state_rows, logits.shape[1], logits.device)
+        sec = stage_section(hb, logits.device, (lambda a: _stage(a, logits.device)) if logits.is_cuda
+                            else torch.from_numpy)
+        if sec["update"]:
+            ops.logit_state_update(state, sec["ids"], sec["cu_seqlens"], sec["procs"], sec["bias_cu"],
+                                   sec["bias_ids"], sec["bias_vals"])
+        ops.apply_logit_processors(logits, state, sec["procs"], sec["seq_lens"], -1 if eos_id is None else eos_id)
     ids = sample(logits, **hb.sampling_args())
+    if sec is not None:
+        ids = ids.to(torch.int32)
+        ops.logit_state_count(state, ids, sec["procs"])
     if hb.logprobs is None:
         return ids, None
     want = np.ascontiguousarray(hb.logprobs, dtype=np.int32)

@@ -33,12 +33,15 @@ class Step:
     the slot's decode rows (``rows`` / ``packed``, one token each, first in the batch) and a bounded
     prefill chunk over ``seqs``."""
 
-    __slots__ = ("is_prefill", "_seqs", "slot", "rows", "packed", "keep", "_live", "mixed")
+    __slots__ = ("is_prefill", "_seqs", "slot", "rows", "packed", "keep", "_live", "mixed", "state_rows")
 
     def __init__(self, is_prefill: bool, seqs: Optional[List[Sequence]] = None, slot: int = 0,
                  rows: Optional[np.ndarray] = None, packed: Optional[np.ndarray] = None,
                  keep: Optional[np.ndarray] = None, live: Optional[Dict[int, Sequence]] = None,
-                 mixed: bool = False):
+                 mixed: bool = False, state_rows: int = 0):
+        # state_rows: the LogitState row count while any request holds a state row, else 0 (the
+        # step's batch then gets no processors section and nobody looks at its sequences for one)
+        self.state_rows = state_rows
         self.is_prefill = is_prefill
         self._seqs = seqs
         self.slot = slot
@@ -96,7 +99,8 @@ class Scheduler:
     MIN_CHUNK = 32          # smallest chunk worth starting in a step whose budget is nearly used
 
     def __init__(self, block_manager, num_slots: int = 1, max_batch: int = 256,
-                 max_prefill_tokens: int = 16384, max_seq_len: int = 4096, mixed_prefill_tokens: int = 0):
+                 max_prefill_tokens: int = 16384, max_seq_len: int = 4096, mixed_prefill_tokens: int = 0,
+                 state_rows: int = 0):
         """``mixed_prefill_tokens`` > 0: a slot with running sequences admits waiting prompts as a
         chunk of at most this many tokens (capped by ``max_prefill_tokens``) riding along with its
         decode rows (a mixed step) instead of a prefill-only step that stalls every running
@@ -117,6 +121,21 @@ class Scheduler:
         self.finished: List[Sequence] = []
         self.num_preemptions = 0
         self.num_prefilling = 0                       # admitted, prefill step not completed yet
+        # LogitState rows (engine/logit_state.py), one per admitted request with logit processors.
+        # Default: every decode row of every slot asking, plus two per slot for the rows a finish
+        # leaves in quarantine (512 KB of device memory per row at a 128k vocabulary, allocated
+        # only once a request asks).  A released row may still be named by a step in flight (a
+        # lookahead step's throw-away row counts its token into it), so it is handed out again
+        # only after every step issued before the release has completed: steps complete in issue
+        # order, so two counters say when
+        if max_seq_len >= 1 << 24:
+            raise ValueError("max_seq_len must be below 2^24 (the LogitState output counts are 24-bit)")
+        self.state_rows = int(state_rows) if state_rows > 0 else self.num_slots * (max_batch + 2)
+        self._free_rows: List[int] = list(range(self.state_rows - 1, -1, -1))
+        self._quarantine: Deque = collections.deque()     # (steps issued at release, row)
+        self._rows_held = 0
+        self._issued = 0
+        self._completed = 0
 
     # ------------------------------------------------------------ requests
     def add(self, seq: Sequence) -> None:
@@ -132,6 +151,7 @@ class Scheduler:
             if s.seq_id == seq_id:
                 self.waiting.remove(s)
                 self.bm.free_sequence(s.seq_id)       # a partly prefilled prompt holds blocks
+                self._release_row(s)
                 s.finish("abort")
                 self.finished.append(s)
                 return True
@@ -139,6 +159,32 @@ class Scheduler:
             self._sync_finished(time.perf_counter())
             return True
         return False
+
+    # ------------------------------------------------------------ LogitState rows
+    def _take_row(self, seq: Sequence) -> bool:
+        """A state row for ``seq`` if it asks for logit processors and has none yet; False when it
+        has to wait for one."""
+        if seq.state_row >= 0 or not seq.params.has_processors:
+            return True
+        q = self._quarantine
+        while q and q[0][0] <= self._completed:
+            self._free_rows.append(q.popleft()[1])
+        if not self._free_rows:
+            return False
+        seq.state_row = self._free_rows.pop()
+        self._rows_held += 1
+        return True
+
+    def _release_row(self, seq: Sequence) -> None:
+        if seq.state_row >= 0:
+            self._quarantine.append((self._issued, seq.state_row))
+            seq.state_row = -1
+            self._rows_held -= 1
+
+    def _step(self, *args, **kw) -> Step:
+        """A step about to be handed out (every one of them comes back through complete())."""
+        self._issued += 1
+        return Step(*args, state_rows=self.state_rows if self._rows_held else 0, **kw)
 
     def has_work(self) -> bool:
         return bool(self.waiting) or self.native.num_running_total() > 0
@@ -186,6 +232,8 @@ class Scheduler:
                 if budget <= 0:
                     break
                 n = budget
+            if not self._take_row(seq):
+                break               # every LogitState row is held or in quarantine: the request waits
             seq.chunk = n if n < seq.total_len - seq.num_cached else 0
             if not self.bm.ensure_capacity(seq.seq_id, seq.num_cached + n):
                 seq.chunk = 0
@@ -214,14 +262,14 @@ class Scheduler:
                 if admitted:
                     self.num_prefilling += len(admitted)
                     self.num_mixed += 1
-                    return Step(True, admitted, slot, rows=rows, packed=packed, live=self.live, mixed=True)
-                return Step(False, None, slot, rows=rows, packed=packed, live=self.live)
+                    return self._step(True, admitted, slot, rows=rows, packed=packed, live=self.live, mixed=True)
+                return self._step(False, None, slot, rows=rows, packed=packed, live=self.live)
             n_running = self.native.num_running(slot)
         if self.waiting:
             admitted, blocked = self._admit(slot, n_running, self.max_prefill_tokens)
             if admitted:
                 self.num_prefilling += len(admitted)
-                return Step(True, admitted, slot)
+                return self._step(True, admitted, slot)
             if blocked and _retry and self._break_kv_deadlock():
                 return self.schedule(slot, _retry=False)
         if not n_running:
@@ -233,7 +281,7 @@ class Scheduler:
         if res is None:
             return None
         packed, rows, _ = res
-        return Step(False, None, slot, rows=rows, packed=packed, live=self.live)
+        return self._step(False, None, slot, rows=rows, packed=packed, live=self.live)
 
     def _break_kv_deadlock(self) -> bool:
         """The head of the queue cannot get KV blocks.  While anything runs or a prefill is in
@@ -258,6 +306,7 @@ class Scheduler:
         # nothing else holds blocks: the pool cannot hold the head's next chunk at all
         self.waiting.popleft()
         self.bm.free_sequence(head.seq_id)
+        self._release_row(head)
         head.finish("kv_capacity")
         self.finished.append(head)
         return True
@@ -271,7 +320,7 @@ class Scheduler:
         if res is None:
             return None
         packed, rows, keep = res
-        return Step(False, None, slot, rows=rows, packed=packed, keep=keep, live=self.live)
+        return self._step(False, None, slot, rows=rows, packed=packed, keep=keep, live=self.live)
 
     def _sync_preempted(self):
         for sid in self.native.take_preempted():
@@ -292,6 +341,7 @@ class Scheduler:
             seq.output.extend(toks.tolist())
             seq.token_times.extend(times.tolist())
             seq.finish(reason, float(times[-1]) if len(times) else now)
+            self._release_row(seq)
             self.finished.append(seq)
             done.append(seq)
         return done
@@ -314,6 +364,12 @@ class Scheduler:
         (chosen [B], top_ids [B, N], top_lp [B, N]) of the step's rows when one of them asked
         (engine/sampler.py unpack_ids_message), else None."""
         now = time.perf_counter() if now is None else now
+        try:
+            return self._complete(step, tokens, now, logprobs)
+        finally:
+            self._completed += 1
+
+    def _complete(self, step: Step, tokens, now: float, logprobs) -> List[Sequence]:
         if not step.is_prefill:
             toks = np.asarray(tokens, dtype=np.int32)
             if logprobs is not None:
@@ -357,6 +413,7 @@ class Scheduler:
                 if not seq.finished:
                     seq.finish("max_seq_len", now)
                 self.bm.free_sequence(seq.seq_id)
+                self._release_row(seq)
                 self.finished.append(seq)
                 done.append(seq)
                 continue

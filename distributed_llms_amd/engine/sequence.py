@@ -9,9 +9,10 @@ from __future__ import annotations
 
 import enum
 import itertools
+import math
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 
 class SeqStatus(enum.Enum):
@@ -32,6 +33,19 @@ class SamplingParams:
     # per-token log-probabilities of the model's distribution: None = off, 0 = the chosen token's
     # only, 1..MAX_LOGPROBS = that many most likely alternatives too (validate_logprobs)
     logprobs: Optional[int] = None
+    # logit processors (validate_processors; contract in ops/reference.py), applied to the logits
+    # before greedy / sampled selection and before logprobs are taken.  The defaults mean "off"
+    repetition_penalty: float = 1.0     # > 0; over prompt + output tokens
+    presence_penalty: float = 0.0       # [-2, 2]; over output tokens
+    frequency_penalty: float = 0.0      # [-2, 2]; times the output count
+    logit_bias: Optional[Dict[int, float]] = None    # <= MAX_LOGIT_BIAS entries, values in [-100, 100]
+    min_tokens: int = 0                 # EOS cannot be drawn before this many output tokens
+
+    @property
+    def has_processors(self) -> bool:
+        """Whether the request asks for any logit processor (it then holds a LogitState row)."""
+        return (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+                or bool(self.logit_bias) or self.min_tokens > 0)
 
     def to_dict(self):
         return dict(self.__dict__)
@@ -52,6 +66,66 @@ def validate_logprobs(value) -> Optional[int]:
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= MAX_LOGPROBS:
         raise ValueError(f"logprobs must be an integer from 0 to {MAX_LOGPROBS}, got {value!r}")
     return value
+
+
+MAX_LOGIT_BIAS = 300   # ops.reference.MAX_LOGIT_BIAS: bias entries of one request
+PROCESSOR_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "min_tokens")
+
+
+def _number(name: str, value, lo: float, hi: float, lo_open: bool = False) -> float:
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) \
+            or not (lo < value if lo_open else lo <= value) or not value <= hi:
+        raise ValueError(f"{name} must be a number in {'(' if lo_open else '['}{lo:g}, {hi:g}], got {value!r}")
+    return float(value)
+
+
+def validate_processors(params, vocab_size: int) -> bool:
+    """The logit-processor fields of ``params`` (a SamplingParams, or a dict of its fields as the
+    master and the HTTP front end hold them) as the engines take them; ``logit_bias`` is normalised
+    in place to {int id: float} (JSON delivers string keys).  Returns whether the request asks for
+    any processor; a bad value raises ValueError."""
+    is_dict = isinstance(params, dict)
+    defaults = SamplingParams.__dataclass_fields__
+
+    def get(k):
+        return params.get(k, defaults[k].default) if is_dict else getattr(params, k)
+
+    def put(k, v):
+        if is_dict:
+            if k in params:
+                params[k] = v
+        else:
+            setattr(params, k, v)
+
+    rep = _number("repetition_penalty", get("repetition_penalty"), 0.0, math.inf, lo_open=True)
+    pres = _number("presence_penalty", get("presence_penalty"), -2.0, 2.0)
+    freq = _number("frequency_penalty", get("frequency_penalty"), -2.0, 2.0)
+    for k, x in (("repetition_penalty", rep), ("presence_penalty", pres), ("frequency_penalty", freq)):
+        put(k, x)
+    bias = get("logit_bias")
+    if bias is not None:
+        if not isinstance(bias, dict) or len(bias) > MAX_LOGIT_BIAS:
+            raise ValueError(f"logit_bias must be an object of at most {MAX_LOGIT_BIAS} entries")
+        norm: Dict[int, float] = {}
+        for k, x in bias.items():
+            try:
+                if isinstance(k, (bool, float)):
+                    raise ValueError
+                t = int(k)
+            except (TypeError, ValueError):
+                raise ValueError(f"logit_bias key {k!r} is not a token id") from None
+            if not 0 <= t < vocab_size:
+                raise ValueError(f"logit_bias token id {t} outside [0, {vocab_size})")
+            if t in norm:
+                raise ValueError(f"logit_bias names token id {t} twice")
+            norm[t] = _number(f"logit_bias[{t}]", x, -100.0, 100.0)
+        bias = norm or None
+        put("logit_bias", bias)
+    mt = get("min_tokens")
+    max_new = get("max_new_tokens")
+    if isinstance(mt, bool) or not isinstance(mt, int) or not 0 <= mt <= max_new:
+        raise ValueError(f"min_tokens must be an integer from 0 to max_new_tokens ({max_new}), got {mt!r}")
+    return rep != 1.0 or pres != 0.0 or freq != 0.0 or bool(bias) or mt > 0
 
 
 _ids = itertools.count(1)
@@ -98,6 +172,9 @@ class Sequence:
     seed: int = 0
     # requests with params.logprobs set: one (chosen_lp, top_ids, top_lps) per generated token
     logprobs: List[tuple] = field(default_factory=list)
+    # requests with logit processors: their LogitState row, handed out by the Scheduler at admission,
+    # kept through preemption, released at finish or abort (-1: none)
+    state_row: int = -1
 
     def __post_init__(self):
         if not self.prompt:

@@ -10,15 +10,22 @@ dependency; every request thread only submits to the master's request futures):
   GET  /metrics                Prometheus text: request metrics + per-worker gauges (HBM, KV blocks,
                                running / waiting sequences, microbatches executed)
   POST /generate               {"prompt": str | "prompt_ids": [int], "max_new_tokens", "temperature",
-                                "top_k", "top_p", "ignore_eos", "logprobs"} -> {"tokens", "text",
-                                "latency_s", ...}; with "logprobs": n (0..20) also "logprobs":
-                                {"token_logprobs", "top_ids", "top_logprobs"}
+                                "top_k", "top_p", "ignore_eos", "logprobs", "repetition_penalty",
+                                "presence_penalty", "frequency_penalty", "logit_bias", "min_tokens"} ->
+                                {"tokens", "text", "latency_s", ...}; with "logprobs": n (0..20) also
+                                "logprobs": {"token_logprobs", "top_ids", "top_logprobs"}
   POST /v1/completions         OpenAI-style: {"prompt": str | [int] | [str...], "max_tokens", ...}
                                -> {"object": "text_completion", "choices": [...], "usage": {...}};
                                "logprobs": n (0..20) adds to each choice the legacy object {"tokens",
                                "token_logprobs", "top_logprobs": [{text: lp}], "text_offset"} plus
                                "token_ids" / "top_token_ids" (two ids can decode to the same text);
                                -inf is serialised as null
+  logit processors             (either POST, also with "stream") "repetition_penalty" (> 0, over prompt and
+                               output tokens), "presence_penalty" / "frequency_penalty" ([-2, 2], over output
+                               tokens), "logit_bias" ({"token id": bias in [-100, 100]}, at most 300 entries,
+                               OpenAI's string keys), "min_tokens" (no EOS before that many tokens).  They
+                               rewrite the logits that greedy selection, sampling and "logprobs" then see;
+                               a value out of range: 400
   "stream": true               (either POST, one prompt) server-sent events: one ``data: {...}`` event
                                per pipeline step that produced tokens (TOKENS messages from stage 0),
                                then ``data: [DONE]`` (not together with "logprobs": 400)
@@ -35,15 +42,16 @@ import time
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from typing import Any, Dict, List, Tuple
 
-from ..engine.sequence import validate_logprobs
+from ..engine.sequence import PROCESSOR_KEYS, validate_logprobs, validate_processors
 from ..utils.metrics import cluster_prometheus_text
 
 log = logging.getLogger("dllm.http")
 
-_PARAM_KEYS = ("temperature", "top_k", "top_p", "ignore_eos", "seed", "logprobs")
+_PARAM_KEYS = ("temperature", "top_k", "top_p", "ignore_eos", "seed", "logprobs") + PROCESSOR_KEYS
 
 
-def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_new_tokens") -> Dict[str, Any]:
+def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_new_tokens",
+              vocab_size: int = 1 << 31) -> Dict[str, Any]:
     p = {k: body[k] for k in _PARAM_KEYS if k in body}
     p["max_new_tokens"] = int(body.get(max_key, body.get("max_new_tokens", default_max)))
     if p["max_new_tokens"] < 1:
@@ -51,6 +59,7 @@ def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_n
     validate_logprobs(p.get("logprobs"))
     if p.get("logprobs") is not None and body.get("stream"):
         raise ValueError("logprobs are not available with stream")
+    validate_processors(p, vocab_size)       # logit_bias arrives with string keys: {int: float} from here on
     return p
 
 
@@ -148,7 +157,7 @@ class _Handler(BaseHTTPRequestHandler):
         if not ids:
             raise ValueError("empty prompt")
         params = _sampling(body, default_max=16 if completions else 64,
-                           max_key="max_tokens" if completions else "max_new_tokens")
+                           max_key="max_tokens" if completions else "max_new_tokens", vocab_size=self._vocab())
         gen = self.master.stream(ids, timeout=self.timeout_s, **params)
         first = next(gen, None)                       # errors before the first byte -> HTTP status
         self.send_response(200)
@@ -178,6 +187,10 @@ class _Handler(BaseHTTPRequestHandler):
         self.wfile.flush()
         self.close_connection = True
 
+    def _vocab(self) -> int:
+        cfg = getattr(self.master, "model_config", None)
+        return int(cfg.vocab_size) if cfg is not None else 1 << 31
+
     def _ids(self, prompt) -> List[int]:
         if isinstance(prompt, str):
             return self.master.tokenizer.encode(prompt)
@@ -201,7 +214,7 @@ class _Handler(BaseHTTPRequestHandler):
 
     def _generate(self, body: Dict[str, Any]) -> Dict[str, Any]:
         ids = body["prompt_ids"] if "prompt_ids" in body else self._ids(body.get("prompt", ""))
-        r = self._run([self._ids(ids)], _sampling(body))[0]
+        r = self._run([self._ids(ids)], _sampling(body, vocab_size=self._vocab()))[0]
         if "logprobs" in r:
             r["logprobs"] = _generate_logprobs(r["logprobs"])
         return r
@@ -212,7 +225,7 @@ class _Handler(BaseHTTPRequestHandler):
             prompts = [self._ids(p) for p in prompt]           # a batch of prompts
         else:
             prompts = [self._ids(prompt)]
-        res = self._run(prompts, _sampling(body, default_max=16, max_key="max_tokens"))
+        res = self._run(prompts, _sampling(body, default_max=16, max_key="max_tokens", vocab_size=self._vocab()))
         choices = [{"index": i, "text": r["text"], "tokens": r["tokens"],
                     "finish_reason": "length" if r.get("finish_reason") in ("length", "max_seq_len") else "stop"}
                    for i, r in enumerate(res)]

@@ -32,7 +32,7 @@ import time
 from typing import Any, Dict, List, Optional, Sequence
 
 from ..config import EngineConfig, ModelConfig, get_model_config
-from ..engine.sequence import validate_logprobs
+from ..engine.sequence import validate_logprobs, validate_processors
 from ..network.protocol import MessageProtocol, pack_ids, unpack_ids, unpack_result
 from ..utils.metrics import RequestMetrics
 from ..utils.tokenizer import get_tokenizer
@@ -535,6 +535,7 @@ class MasterNode:
         validate_logprobs(params.get("logprobs"))      # a bad value fails here, not on the stage-0 worker
         if params.get("logprobs") is not None and params.get("stream"):
             raise ValueError("logprobs are not available with stream")
+        validate_processors(params, self.model_config.vocab_size if self.model_config else 1 << 31)     # normalises logit_bias to {int: float}
         with self._lock:
             # degraded with recovery on: hold the request with the parked in-flight ones (bounded)
             # until the stage is re-admitted (plan.md:430-436) -- checked under the

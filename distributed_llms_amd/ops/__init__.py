@@ -24,7 +24,8 @@ __all__ = [
     "embedding", "rms_norm", "fused_add_rms_norm", "layer_norm", "linear", "silu_mul",
     "gelu_tanh", "rope_cache_append", "paged_attention_decode", "paged_attention_prefill",
     "argmax", "add_", "moe_route", "moe_mlp", "decode_split_plan", "paged_attention_decode_rope",
-    "paged_attention_prefill_rope", "sample_rows", "token_logprobs",
+    "paged_attention_prefill_rope", "sample_rows", "token_logprobs", "logit_state_update",
+    "apply_logit_processors", "logit_state_count",
 ]
 
 
@@ -545,6 +546,104 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, 
     _ext.kernels().token_logprobs(chosen.data_ptr(), top_ids.data_ptr(), top_lp.data_ptr(), logits.data_ptr(), rows, v,
                                   logits.stride(0), ids.data_ptr(), want.data_ptr(), n_max, _stream())
     return chosen, top_ids, top_lp
+
+
+# ------------------------------------------------------------ logit processors
+# Penalties, logit_bias and the min_tokens EOS ban (contract: ops/reference.py).  ``ls`` is an
+# engine.logit_state.LogitState (or anything with its tensors): state [rows, pitch] int32, bias_n
+# [rows] int32, bias_ids [rows, P] int32, bias_vals [rows, P] float32, and ``vocab``.
+def _fused_processors(logits_like: torch.Tensor, vocab: int) -> bool:
+    return _gpu(logits_like) and knobs.K.fused_sampler and vocab <= SAMPLE_MAX_VOCAB
+
+
+def _ck_state(ls, op: str, procs: torch.Tensor, rows: int):
+    _ck(ls.state, f"{op}.state", torch.int32)
+    _ck(procs, f"{op}.procs", torch.int32)
+    if procs.shape != (rows, ref.PROC_WORDS):
+        raise ValueError(f"{op}: procs must be [{rows}, {ref.PROC_WORDS}]")
+    if ls.state.dim() != 2 or ls.state.shape[1] % 8 or ls.state.shape[1] < ls.vocab:
+        raise ValueError(f"{op}: state must be [rows, pitch], pitch a multiple of 8 covering the vocabulary")
+    _ck(ls.bias_n, f"{op}.bias_n", torch.int32)
+    _ck(ls.bias_ids, f"{op}.bias_ids", torch.int32)
+    _ck(ls.bias_vals, f"{op}.bias_vals", torch.float32)
+    n = ls.state.shape[0]
+    if ls.bias_n.shape != (n,) or ls.bias_ids.dim() != 2 or ls.bias_ids.shape[0] != n \
+            or ls.bias_vals.shape != ls.bias_ids.shape:
+        raise ValueError(f"{op}: bias_n / bias_ids / bias_vals must be [{n}] / [{n}, P] / [{n}, P]")
+    if any(t.device != ls.state.device for t in (procs, ls.bias_n, ls.bias_ids, ls.bias_vals)):
+        raise ValueError(f"{op}: procs and the bias tensors must be on the state's device")
+
+
+def logit_state_update(ls, ids: torch.Tensor, cu_seqlens: torch.Tensor, procs: torch.Tensor,
+                       step_bias_cu: torch.Tensor, step_bias_ids: torch.Tensor, step_bias_vals: torch.Tensor) -> None:
+    """A step's prefill chunks enter the state: ids [T] int32, cu_seqlens [B + 1] int32, procs
+    [B, PROC_WORDS] int32 (rows with PROC_UPDATE and a state row take part; PROC_START is the
+    position of the chunk's first token), step_bias_* the bias lists of the step (cu [B + 1], ids
+    and float32 values [n]) that chunks starting at position 0 install."""
+    rows = procs.shape[0]
+    _ck_state(ls, "logit_state_update", procs, rows)
+    _ck(ids, "logit_state_update.ids", torch.int32)
+    _ck(cu_seqlens, "logit_state_update.cu_seqlens", torch.int32)
+    _ck(step_bias_cu, "logit_state_update.step_bias_cu", torch.int32)
+    _ck(step_bias_ids, "logit_state_update.step_bias_ids", torch.int32)
+    _ck(step_bias_vals, "logit_state_update.step_bias_vals", torch.float32)
+    if cu_seqlens.shape != (rows + 1,) or step_bias_cu.shape != (rows + 1,) \
+            or step_bias_ids.shape != step_bias_vals.shape or step_bias_ids.dim() != 1:
+        raise ValueError("logit_state_update: cu_seqlens / step_bias_cu must be [B + 1], the bias lists [n]")
+    if any(t.device != ls.state.device for t in (ids, cu_seqlens, step_bias_cu, step_bias_ids, step_bias_vals)):
+        raise ValueError("logit_state_update: every tensor must be on the state's device")
+    if not _fused_processors(ls.state, ls.vocab):
+        return ref.logit_state_update(ls.state, ls.vocab, ids, cu_seqlens, procs, ls.bias_n, ls.bias_ids,
+                                      ls.bias_vals, step_bias_cu, step_bias_ids, step_bias_vals)
+    _ext.kernels().logit_state_update(ls.state.data_ptr(), ls.state.shape[1], ls.state.shape[0], ls.vocab,
+                                      ids.data_ptr(), cu_seqlens.data_ptr(), procs.data_ptr(), rows,
+                                      ls.bias_n.data_ptr(), ls.bias_ids.data_ptr(), ls.bias_vals.data_ptr(),
+                                      ls.bias_ids.shape[1], step_bias_cu.data_ptr(), step_bias_ids.data_ptr(),
+                                      step_bias_vals.data_ptr(), _stream())
+
+
+def apply_logit_processors(logits: torch.Tensor, ls, procs: torch.Tensor, seq_lens: torch.Tensor,
+                           eos_id: int) -> torch.Tensor:
+    """The processors on ``logits`` [B, V], in place, for the rows with PROC_SAMPLE and a state row;
+    every other row is neither read nor written.  seq_lens [B] int32: a row draws output token
+    number seq_lens - prompt_len, and ``eos_id`` (-1: none) is banned while that is < min_tokens.
+    bf16 CUDA logits with a contiguous last dim of at most SAMPLE_MAX_VOCAB entries take the HIP
+    kernel (with ``knobs.fused_sampler`` on); anything else the reference."""
+    if logits.dim() != 2 or logits.shape[1] != ls.vocab:
+        raise ValueError(f"apply_logit_processors: logits must be [B, {ls.vocab}]")
+    rows, v = logits.shape
+    _ck_state(ls, "apply_logit_processors", procs, rows)
+    _ck(seq_lens, "apply_logit_processors.seq_lens", torch.int32)
+    if seq_lens.shape != (rows,) or seq_lens.device != logits.device or ls.state.device != logits.device:
+        raise ValueError("apply_logit_processors: seq_lens must be [B]; everything on the logits' device")
+    eos_id = -1 if eos_id is None else int(eos_id)
+    if not -1 <= eos_id < v:
+        raise ValueError(f"apply_logit_processors: eos id {eos_id} outside the vocabulary")
+    if not (_fused_processors(logits, v) and logits.dtype == torch.bfloat16 and logits.stride(-1) == 1
+            and (rows <= 1 or logits.stride(0) >= v)):
+        if _gpu(logits):
+            _warn_host_sampler(logits, "apply_logit_processors")
+        ref.apply_logit_processors(logits, ls.state, procs, seq_lens, eos_id, ls.bias_n, ls.bias_ids, ls.bias_vals)
+        return logits
+    _ext.kernels().apply_logit_processors(logits.data_ptr(), rows, v, max(logits.stride(0), v), ls.state.data_ptr(),
+                                          ls.state.shape[1], ls.state.shape[0], procs.data_ptr(), seq_lens.data_ptr(),
+                                          eos_id, ls.bias_n.data_ptr(), ls.bias_ids.data_ptr(),
+                                          ls.bias_vals.data_ptr(), ls.bias_ids.shape[1], _stream())
+    return logits
+
+
+def logit_state_count(ls, ids: torch.Tensor, procs: torch.Tensor) -> None:
+    """After sampling: ids [B] int32, the id each row drew; rows with PROC_SAMPLE and a state row
+    add one to that id's count."""
+    rows = procs.shape[0]
+    _ck_state(ls, "logit_state_count", procs, rows)
+    _ck(ids, "logit_state_count.ids", torch.int32)
+    if ids.shape != (rows,) or ids.device != ls.state.device:
+        raise ValueError(f"logit_state_count: ids must be [{rows}] on the state's device")
+    if not _fused_processors(ls.state, ls.vocab):
+        return ref.logit_state_count(ls.state, ls.vocab, ids, procs)
+    _ext.kernels().logit_state_count(ls.state.data_ptr(), ls.state.shape[1], ls.state.shape[0], ls.vocab,
+                                     ids.data_ptr(), procs.data_ptr(), rows, _stream())
 
 
 # ------------------------------------------------------------ K11/K12

@@ -398,6 +398,161 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, 
             torch.from_numpy(tl).to(torch.float32).to(dev))
 
 
+# ------------------------------------------------------------------ logit processors
+# The contract of csrc/kernels/logit_processors.hip, in numpy float32.  Two per-token quantities of
+# a request drive it: in_prompt[t] (t occurs in its prompt) and n_out[t] (how often t occurs in its
+# outputs so far; outputs recomputed as "prompt" after a preemption still count as outputs).  For
+# every token t that some rule touches, each operation rounded to float32 on its own (no fused
+# multiply-add, a correctly rounded divide):
+#   x = f32(logit[t])
+#   if (in_prompt[t] or n_out[t] > 0) and rep != 1:  x = x / rep if x > 0 else x * rep
+#   if n_out[t] > 0:  x = x - (freq * f32(n_out[t]));  x = x - pres
+#   if t in bias:     x = x + bias[t]
+#   if t == eos and (index of the output token being drawn) < min_tokens:  x = -inf
+#   logit[t] = round(x)   ONE rounding to the logits' type (bf16: nearest even), whatever applied
+# A token no rule touches keeps its bits (-0, NaN payloads); NaN in stays NaN.  Repetition runs over
+# prompt + output, presence and frequency over output only (vLLM's semantics).
+#
+# Device state: one int32 word per (state row, token): output count | STATE_BIAS_BIT |
+# STATE_PROMPT_BIT; procs [B, PROC_WORDS] int32 per step row (PROC_* word indices below).
+PROC_WORDS = 8
+PROC_ROW, PROC_PROMPT_LEN, PROC_FLAGS, PROC_REP, PROC_PRES, PROC_FREQ, PROC_MIN_TOKENS, PROC_START = range(8)
+PROC_SAMPLE = 1        # flag: apply the processors to the row and count the id it draws
+PROC_UPDATE = 2        # flag: the row is a prefill chunk whose tokens enter the state
+STATE_COUNT_MASK = 0x00FFFFFF
+STATE_BIAS_BIT = 1 << 29
+STATE_PROMPT_BIT = 1 << 31
+MAX_LOGIT_BIAS = 300
+
+
+def bf16_rne_bits(x):
+    """float32 array -> bf16 bit patterns (uint16), round to nearest even; NaN stays a (quiet) NaN."""
+    import numpy as np
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    r = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, ((u >> np.uint32(16)) | np.uint32(0x40)).astype(np.uint16), r)
+
+
+def logit_processors_row(x, in_prompt, n_out, rep=1.0, pres=0.0, freq=0.0, bias=None, ban_id=-1):
+    """The chain on one row: x [V] float32 (the logits, converted exactly), in_prompt [V] bool,
+    n_out [V] ints, bias {id: value} -> (x' float32 [V], touched bool [V]); entries of x' that are
+    not ``touched`` are meaningless.  ``ban_id`` >= 0: the id that min_tokens bans in this step."""
+    import numpy as np
+    x = np.array(x, dtype=np.float32)
+    v = x.shape[0]
+    n_out = np.asarray(n_out).astype(np.int64)
+    rep, pres, freq = np.float32(rep), np.float32(pres), np.float32(freq)
+    out = n_out > 0
+    touched = out.copy()
+    with np.errstate(all="ignore"):
+        if rep != np.float32(1.0):
+            seen = np.asarray(in_prompt, dtype=bool) | out
+            touched |= seen
+            x = np.where(seen, np.where(x > 0, x / rep, x * rep), x).astype(np.float32)
+        f = (freq * n_out.astype(np.float32)).astype(np.float32)
+        x = np.where(out, ((x - f).astype(np.float32) - pres).astype(np.float32), x)
+        for t, b in (bias or {}).items():
+            t = int(t)
+            if 0 <= t < v:
+                x[t] = x[t] + np.float32(b)
+                touched[t] = True
+    if 0 <= ban_id < v:
+        x[ban_id] = -np.inf
+        touched[ban_id] = True
+    return x, touched
+
+
+def _proc_f32(procs, col):
+    import numpy as np
+    return np.ascontiguousarray(procs[:, col]).view(np.float32)
+
+
+def _state_rows(procs, flag, state_rows):
+    """(step rows, their state rows) of the rows that carry ``flag`` and a valid state row."""
+    import numpy as np
+    sr = procs[:, PROC_ROW]
+    rows = np.nonzero((sr >= 0) & (sr < state_rows) & ((procs[:, PROC_FLAGS] & flag) != 0))[0]
+    return rows, sr[rows].astype(np.int64)
+
+
+@torch.inference_mode()    # the engines' logits are inference tensors; in-place writes need the mode
+def logit_state_update(state, vocab, ids, cu_seqlens, procs, bias_n, bias_ids, bias_vals, step_bias_cu,
+                       step_bias_ids, step_bias_vals) -> None:
+    """Prefill chunks enter the state (in place): a chunk that starts at position 0 zeroes its own
+    state row and installs its bias list; then every chunk token at a position < prompt_len sets the
+    prompt bit, every later one adds one to the count.  Ids outside [0, vocab) are ignored."""
+    import numpy as np
+    pr = procs.detach().cpu().numpy().reshape(-1, PROC_WORDS)
+    rows, srows = _state_rows(pr, PROC_UPDATE, state.shape[0])
+    if rows.shape[0] == 0:
+        return
+    idn, cu = ids.detach().cpu().numpy(), cu_seqlens.detach().cpu().numpy()
+    bcu, bid = step_bias_cu.detach().cpu().numpy(), step_bias_ids.detach().cpu().numpy()
+    for r, s in zip(rows.tolist(), srows.tolist()):
+        st = state[s].detach().cpu().numpy().view(np.uint32).copy()
+        start, plen = int(pr[r, PROC_START]), int(pr[r, PROC_PROMPT_LEN])
+        if start == 0:
+            st[:] = 0
+            a, e = int(bcu[r]), int(bcu[r + 1])
+            n = min(e - a, bias_ids.shape[1])
+            bias_n[s] = n
+            bias_ids[s, :n] = step_bias_ids[a:a + n]
+            bias_vals[s, :n] = step_bias_vals[a:a + n]
+            b = bid[a:a + n]
+            st[b[(b >= 0) & (b < vocab)]] |= np.uint32(STATE_BIAS_BIT)
+        toks = idn[int(cu[r]):int(cu[r + 1])].astype(np.int64)
+        pos = start + np.arange(toks.shape[0])
+        ok = (toks >= 0) & (toks < vocab)
+        st[toks[ok & (pos < plen)]] |= np.uint32(STATE_PROMPT_BIT)
+        np.add.at(st, toks[ok & (pos >= plen)], np.uint32(1))
+        state[s] = torch.from_numpy(st.view(np.int32)).to(state.device)
+
+
+@torch.inference_mode()    # the engines' logits are inference tensors; in-place writes need the mode
+def apply_logit_processors(logits, state, procs, seq_lens, eos_id, bias_n, bias_ids, bias_vals) -> None:
+    """The chain above on every row with PROC_SAMPLE and a state row, in place (logits [B, V] of any
+    float type: bf16 rows are rounded to nearest even, float32 rows not at all)."""
+    import numpy as np
+    pr = procs.detach().cpu().numpy().reshape(-1, PROC_WORDS)
+    rows, srows = _state_rows(pr, PROC_SAMPLE, state.shape[0])
+    if rows.shape[0] == 0:
+        return
+    v = logits.shape[1]
+    sl = seq_lens.detach().cpu().numpy()
+    rep, pres, freq = _proc_f32(pr, PROC_REP), _proc_f32(pr, PROC_PRES), _proc_f32(pr, PROC_FREQ)
+    bn, bi, bv = (t.detach().cpu().numpy() for t in (bias_n, bias_ids, bias_vals))
+    for r, s in zip(rows.tolist(), srows.tolist()):
+        st = state[s, :v].detach().cpu().numpy().view(np.uint32)
+        n = int(bn[s])
+        bias = {int(t): np.float32(b) for t, b in zip(bi[s, :n], bv[s, :n])}
+        ban = int(eos_id) if eos_id >= 0 and int(sl[r]) - int(pr[r, PROC_PROMPT_LEN]) < int(pr[r, PROC_MIN_TOKENS]) else -1
+        row = logits[r]
+        x, touched = logit_processors_row(row.detach().float().cpu().numpy(), (st & np.uint32(STATE_PROMPT_BIT)) != 0,
+                                          st & np.uint32(STATE_COUNT_MASK), rep[r], pres[r], freq[r], bias, ban)
+        if not touched.any():
+            continue
+        if row.dtype == torch.bfloat16:
+            old = row.detach().view(torch.int16).cpu().numpy().view(np.uint16)
+            new = np.where(touched, bf16_rne_bits(x), old)
+            row.copy_(torch.from_numpy(new.view(np.int16)).view(torch.bfloat16).to(row.device))
+        else:
+            idx = torch.from_numpy(np.nonzero(touched)[0]).to(row.device)
+            row[idx] = torch.from_numpy(x[touched]).to(row.device, row.dtype)
+
+
+@torch.inference_mode()    # the engines' logits are inference tensors; in-place writes need the mode
+def logit_state_count(state, vocab, ids, procs) -> None:
+    """After sampling: every row with PROC_SAMPLE and a state row counts the id it drew (in place)."""
+    pr = procs.detach().cpu().numpy().reshape(-1, PROC_WORDS)
+    rows, srows = _state_rows(pr, PROC_SAMPLE, state.shape[0])
+    idn = ids.detach().cpu().numpy()
+    for r, s in zip(rows.tolist(), srows.tolist()):
+        t = int(idn[r])
+        if 0 <= t < vocab:
+            state[s, t] += 1
+
+
 def moe_route(router_logits: torch.Tensor, top_k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Mixtral routing: softmax over experts, top-k, renormalise. -> (weights f32, ids i32)."""
     probs = torch.softmax(router_logits.float(), dim=-1)

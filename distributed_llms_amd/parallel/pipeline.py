@@ -37,7 +37,8 @@ from ..engine.batch import HostBatch, build_host_batch
 from ..engine.runner import StageRunner
 from ..engine.sampler import ids_message_len, sample_step, unpack_ids_message
 from ..engine.scheduler import Scheduler, Step
-from ..engine.sequence import SamplingParams, Sequence, request_seed, validate_logprobs
+from ..engine.logit_state import LogitState
+from ..engine.sequence import SamplingParams, Sequence, request_seed, validate_logprobs, validate_processors
 from ..utils.tracing import get_tracer
 from .comm import STOP, PendingIds, Transport
 
@@ -57,6 +58,7 @@ def stage_worker_loop(runner: StageRunner, transport: Transport, stop_on_round_e
     h = st.in_width
     last = transport.stage == transport.num_stages - 1
     tr = get_tracer()
+    logit_state = LogitState()     # the last stage samples: it owns the logit processors' state
     while True:
         arr = transport.recv_meta()
         if arr.shape[0] == 1 and arr[0] in _MARKERS:
@@ -80,7 +82,7 @@ def stage_worker_loop(runner: StageRunner, transport: Transport, stop_on_round_e
                 transport.send_ids(tp_sample(out, st.tp, hb.sampling_args()))
             else:
                 # a step in which a row asked for log-probabilities answers with its ids message
-                ids, msg = sample_step(out, hb)
+                ids, msg = sample_step(out, hb, logit_state, st.cfg.eos_token_id)
                 transport.send_ids(ids if msg is None else msg)
         else:
             with tr.span("pp.send_hidden", cat="comm", step=hb.step_id):
@@ -115,7 +117,7 @@ class PipelineDriver:
         self.bm = block_manager
         self.num_slots = num_slots or pipeline_slots(ecfg, transport.num_stages, runner.stage.device)
         self.scheduler = Scheduler(block_manager, self.num_slots, ecfg.max_batch, ecfg.max_prefill_tokens,
-                                   ecfg.max_seq_len, ecfg.mixed_prefill_tokens)
+                                   ecfg.max_seq_len, ecfg.mixed_prefill_tokens, ecfg.logit_state_rows)
         self.mcfg = runner.stage.cfg
         self.device = runner.stage.device
         self.inflight: Deque[_Issued] = collections.deque()           # issue order
@@ -134,6 +136,8 @@ class PipelineDriver:
         params = params or SamplingParams()
         if validate_logprobs(params.logprobs) is not None and self.tp is not None:
             raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
+        if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
+            raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
         seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id)
         seq.seed = request_seed(seq.params, self._seed_rng)
         self.scheduler.add(seq)

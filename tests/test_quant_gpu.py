@@ -102,7 +102,7 @@ def test_fp8_engine_generates_and_tracks_bf16():
     assert s.weight_bytes() < build_stage(ecfg, device=DEV).weight_bytes()
 
 
-@pytest.mark.parametrize("hidden", [4096, 256, 8192])
+@pytest.mark.parametrize("hidden", [4096, 256, 8192, 136, 2056, 8200, 16384])
 def test_norm_kernels_emit_the_same_fp8_as_quantizing_their_output(hidden):
     """rms_norm / fused_add_rms_norm / splitk_add_rms_norm with quant_out: bit-identical to the
     bf16 output quantized by quant_fp8_rows (the epilogue rounds to bf16 first)."""

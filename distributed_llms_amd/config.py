@@ -255,6 +255,10 @@ class EngineConfig:
     kv_block_size: int = 32            # tokens per paged-KV block
     kv_cache_fraction: float = 0.80    # of free HBM after weights
     num_kv_blocks: int = 0             # 0 -> derive from kv_cache_fraction
+    # automatic prefix caching: full prompt blocks stay in the paged cache under a chained content key
+    # and a later request with the same prefix prefills only its tail (csrc/runtime/block_manager.h,
+    # engine/scheduler.py).  Not with tensor parallelism (tp > 1)
+    enable_prefix_caching: bool = False
     use_graphs: bool = True            # HIP-graph capture of the decode step
     quant: str = "none"                # "fp8": W8A8 e4m3 dense projections (ops/quant.py)
     # pipeline activation transport between GPU stages: "auto" (= "rccl" on GPUs), "rccl" (native
@@ -302,6 +306,12 @@ class EngineConfig:
         cfg = get_model_config(self.model if self.shard_dir is None else self.shard_dir)
         if self.num_workers > cfg.num_layers:
             raise ValueError(f"{self.num_workers} stages > {cfg.num_layers} layers")
+
+    def check_tensor_parallel(self, tp: int) -> None:
+        """What a tensor-parallel layout (``tp`` ranks per stage) cannot run; every rank calls it with the
+        same arguments before it builds anything, so all of them refuse together."""
+        if tp > 1 and self.enable_prefix_caching:
+            raise ValueError("prefix caching is not supported with tensor parallelism (tp > 1)")
 
     def model_config(self) -> ModelConfig:
         return get_model_config(self.shard_dir or self.model)

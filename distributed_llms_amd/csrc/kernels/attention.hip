@@ -495,25 +495,21 @@ __device__ __forceinline__ void xcd_order(int& qt, int& kvh, int& b) {
 // Prefill v3: each wave owns NT column tiles (NT x 16/G query rows x G heads) and walks the
 // KV chunks with the decode kernel's depth-2 pipeline (chunk c+1's K/V loads in flight while
 // chunk c's MFMAs run), so every loaded chunk serves NT tiles and its load latency is hidden.
+// prefill2_walk is the wave's whole main part -- its q tiles, the causal bound per column, the walk
+// over the chunks [split * split_chunks, ...) below the wave's own causal bound -- shared with the
+// split-context form below; v3 itself is the one split that covers everything.
 // ---------------------------------------------------------------------------
 template <int D, int G, int NT>
-__global__ void __launch_bounds__(256, NT == 1 ? 2 : 1) attn_prefill2_kernel(
-    bf16* __restrict__ out, const bf16* __restrict__ q, const bf16* __restrict__ k_cache,
-    const bf16* __restrict__ v_cache, const int32_t* __restrict__ block_tables,
-    const int32_t* __restrict__ cu_seqlens_q, const int32_t* __restrict__ seq_lens, int hq, int hkv,
-    int max_blocks, float scale_log2) {
+__device__ __forceinline__ void prefill2_walk(WaveState<D> (&st)[NT], const bf16* __restrict__ q,
+                                              const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache,
+                                              const int32_t* __restrict__ bt, int qs, int ql, int ctx, int row0,
+                                              int hq, int hkv, int kvh, int split, int nsplit, int split_chunks,
+                                              float scale_log2, int lane) {
   constexpr int R = 16 / G;                       // query rows per column tile
-  const int kvh = blockIdx.y, b = blockIdx.z;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
-  const int qs = cu_seqlens_q[b], ql = cu_seqlens_q[b + 1] - qs;
-  const int row0 = (blockIdx.x * kWaves + w) * (R * NT);
-  if (row0 >= ql) return;                         // wave-uniform
-  const int ctx = seq_lens[b];
   const int qpos0 = ctx - ql;                     // position of row 0
   bf16x8 qf[NT][D / 32];
   int kmax_col[NT];
-  WaveState<D> st[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int crow = row0 + t * R + r / G, ch = r % G;
@@ -529,8 +525,11 @@ __global__ void __launch_bounds__(256, NT == 1 ? 2 : 1) attn_prefill2_kernel(
     init_state(st[t]);
   }
   const int wave_kmax = qpos0 + min(row0 + R * NT, ql) - 1;
-  const int nch = wave_kmax / kBS + 1;            // chunks this wave reads
-  const int32_t* bt = block_tables + (size_t)b * max_blocks;
+  const int nch = wave_kmax / kBS + 1;            // chunks below this wave's causal bound (<= max_blocks)
+  // this split's chunks; the last split runs to the bound whatever the host planned, so no key is
+  // dropped should a sequence be longer than the context the plan was made for
+  const int c0 = min(split * split_chunks, nch);
+  const int c1 = split == nsplit - 1 ? nch : min(c0 + split_chunks, nch);
   const size_t kv_head_stride = (size_t)kBS * D;
   const size_t head_off = (size_t)kvh * kv_head_stride;
   const size_t blk_stride = (size_t)hkv * kv_head_stride;
@@ -538,8 +537,8 @@ __global__ void __launch_bounds__(256, NT == 1 ? 2 : 1) attn_prefill2_kernel(
 #pragma unroll
     for (int t = 0; t < NT; ++t) compute_chunk<D>(st[t], qf[t], c, chunk * kBS, kmax_col[t], scale_log2, lane);
   };
-  for (int cb = 0; cb < nch; cb += 64) {          // 64 chunks of block ids per pass
-    const int n = min(64, nch - cb);
+  for (int cb = c0; cb < c1; cb += 64) {          // 64 chunks of block ids per pass
+    const int n = min(64, c1 - cb);
     const int my_blk = lane < n ? bt[cb + lane] : 0;
     KVChunk<D> cur, nxt;
     {
@@ -561,8 +560,67 @@ __global__ void __launch_bounds__(256, NT == 1 ? 2 : 1) attn_prefill2_kernel(
     }
     if (j < n) compute(cur, cb + j);
   }
+}
+
+template <int D, int G, int NT>
+__global__ void __launch_bounds__(256, NT == 1 ? 2 : 1) attn_prefill2_kernel(
+    bf16* __restrict__ out, const bf16* __restrict__ q, const bf16* __restrict__ k_cache,
+    const bf16* __restrict__ v_cache, const int32_t* __restrict__ block_tables,
+    const int32_t* __restrict__ cu_seqlens_q, const int32_t* __restrict__ seq_lens, int hq, int hkv,
+    int max_blocks, float scale_log2) {
+  constexpr int R = 16 / G;
+  const int kvh = blockIdx.y, b = blockIdx.z;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int qs = cu_seqlens_q[b], ql = cu_seqlens_q[b + 1] - qs;
+  const int row0 = (blockIdx.x * kWaves + w) * (R * NT);
+  if (row0 >= ql) return;                         // wave-uniform
+  WaveState<D> st[NT];
+  prefill2_walk<D, G, NT>(st, q, k_cache, v_cache, block_tables + (size_t)b * max_blocks, qs, ql, seq_lens[b], row0,
+                          hq, hkv, kvh, 0, 1, 0, scale_log2, lane);
 #pragma unroll
   for (int t = 0; t < NT; ++t) store_tile_direct<D, G>(out, st[t], row0 + t * R, qs, ql, hq, kvh, lane);
+}
+
+// ---------------------------------------------------------------------------
+// Prefill v5 (split context): v3 for a few query rows over a long cached context (the tail of a
+// prompt whose prefix was found in the paged cache).  v3's grid there is a handful of workgroups,
+// each walking the whole context; here grid.x = q_tiles * nsplit and a wave walks only the chunks
+// [split * split_chunks, (split + 1) * split_chunks) of its sequence's context -- below its own causal
+// bound, as in v3 -- and writes unnormalised (o, m, l) partials in the decode partial layout, the row
+// being the packed token row.  attn_split_reduce_kernel finishes: its bh * D + d is [T, hq, D].
+// Every (row < ql, head, split) writes its partial, also a split with no admissible key for the row
+// (o = 0, m = -inf, l = 0): the reduce reads nothing it did not get.
+// ---------------------------------------------------------------------------
+template <int D, int G, int NT>
+__global__ void __launch_bounds__(256, NT == 1 ? 2 : 1) attn_prefill_split_kernel(
+    float* __restrict__ part_o, float* __restrict__ part_ml, const bf16* __restrict__ q,
+    const bf16* __restrict__ k_cache, const bf16* __restrict__ v_cache, const int32_t* __restrict__ block_tables,
+    const int32_t* __restrict__ cu_seqlens_q, const int32_t* __restrict__ seq_lens, int hq, int hkv,
+    int max_blocks, int nsplit, int split_chunks, float scale_log2) {
+  constexpr int R = 16 / G;
+  const int kvh = blockIdx.y, b = blockIdx.z;
+  const int split = blockIdx.x % nsplit, qt = blockIdx.x / nsplit;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int qs = cu_seqlens_q[b], ql = cu_seqlens_q[b + 1] - qs;
+  const int row0 = (qt * kWaves + w) * (R * NT);
+  if (row0 >= ql) return;                         // wave-uniform
+  WaveState<D> st[NT];
+  prefill2_walk<D, G, NT>(st, q, k_cache, v_cache, block_tables + (size_t)b * max_blocks, qs, ql, seq_lens[b], row0,
+                          hq, hkv, kvh, split, nsplit, split_chunks, scale_log2, lane);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    float lt = st[t].lsum;
+    lt = rows_sum(lt);
+    const int crow = row0 + t * R + r / G, ch = r % G;
+    if (crow < ql) {                              // after the last MFMA: divergence is safe
+      const size_t pi = ((size_t)(qs + crow) * hq + kvh * G + ch) * nsplit + split;
+      float* po = part_o + pi * D;
+#pragma unroll
+      for (int dt = 0; dt < D / 16; ++dt) *reinterpret_cast<f32x4*>(po + dt * 16 + 4 * g) = st[t].acc[dt];
+      if (g == 0) { part_ml[pi * 2] = st[t].m; part_ml[pi * 2 + 1] = lt; }
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1472,6 +1530,71 @@ void paged_attention_prefill(uintptr_t out, uintptr_t q, uintptr_t k_cache, uint
   else
     launch_prefill<64>(G, version, max_q_len, batch, hkv, s, out, q, k_cache, v_cache, block_tables, cu_seqlens_q,
                        seq_lens, hq, max_blocks, sl2, positions, cos_sin, q_stride);
+  DLLM_HIP_CHECK(hipGetLastError());
+}
+
+template <int D, int NT>
+static void launch_prefill_split(int g, dim3 grid, hipStream_t s, uintptr_t part_o, uintptr_t part_ml, uintptr_t q,
+                                 uintptr_t k_cache, uintptr_t v_cache, uintptr_t bt, uintptr_t cu, uintptr_t sl, int hq,
+                                 int hkv, int max_blocks, int nsplit, int split_chunks, float sl2) {
+#define DLLM_PFS(GG)                                                                                              \
+  hipLaunchKernelGGL((attn_prefill_split_kernel<D, GG, NT>), grid, dim3(kWaves * 64), 0, s, (float*)part_o,       \
+                     (float*)part_ml, (const bf16*)q, (const bf16*)k_cache, (const bf16*)v_cache,                 \
+                     (const int32_t*)bt, (const int32_t*)cu, (const int32_t*)sl, hq, hkv, max_blocks, nsplit,     \
+                     split_chunks, sl2)
+  switch (g) {
+    case 1: DLLM_PFS(1); break;
+    case 2: DLLM_PFS(2); break;
+    case 4: DLLM_PFS(4); break;
+    case 8: DLLM_PFS(8); break;
+    case 16: DLLM_PFS(16); break;
+    default: throw std::runtime_error("prefill attention: GQA group must be 1,2,4,8,16");
+  }
+#undef DLLM_PFS
+}
+
+// Prefill version 5: q [T, hq, D] rotated, the context in the paged cache; part_o [T, hq, nsplit, D] and
+// part_ml [T, hq, nsplit, 2] floats.  Split s of a sequence covers its chunks [s, s + 1) * split_chunks
+// (nsplit * split_chunks must cover the block table's used width: ops.prefill_split_plan).
+void paged_attention_prefill_split(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
+                                   uintptr_t block_tables, uintptr_t cu_seqlens_q, uintptr_t seq_lens,
+                                   uintptr_t part_o, uintptr_t part_ml, int batch, int total_tokens, int hq, int hkv,
+                                   int d, int block_size, int max_blocks, int max_q_len, int max_ctx, int nsplit,
+                                   int split_chunks, float scale, uintptr_t stream) {
+  DLLM_HOST_CHECK(block_size == kBS, "paged attention requires block_size 32");
+  DLLM_HOST_CHECK(d == 64 || d == 128, "head_dim must be 64 or 128");
+  DLLM_HOST_CHECK(hq % hkv == 0, "Hq % Hkv");
+  DLLM_HOST_CHECK(nsplit >= 1 && split_chunks >= 1 && part_o && part_ml, "split plan and workspace");
+  DLLM_HOST_CHECK(max_ctx <= max_blocks * kBS && (long)nsplit * split_chunks * kBS >= max_ctx,
+                  "the splits must cover the longest context");
+  if (batch == 0 || max_q_len == 0 || total_tokens == 0) return;
+  const int G = hq / hkv;
+  DLLM_HOST_CHECK(G >= 1 && G <= 16 && 16 % G == 0, "prefill attention: GQA group must be 1,2,4,8,16");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const float sl2 = scale * 1.4426950408889634f;
+  // one tile per wave while that still covers the rows with one workgroup per sequence and kv head (every
+  // wave busy on a short tail), else v3's two
+  const int nt = max_q_len <= kWaves * (16 / G) ? 1 : 2;
+  const int rows_per_wg = kWaves * (16 / G) * nt;
+  const dim3 grid((unsigned)((max_q_len + rows_per_wg - 1) / rows_per_wg) * nsplit, hkv, batch);
+  if (d == 128) {
+    if (nt == 1) launch_prefill_split<128, 1>(G, grid, s, part_o, part_ml, q, k_cache, v_cache, block_tables,
+                                              cu_seqlens_q, seq_lens, hq, hkv, max_blocks, nsplit, split_chunks, sl2);
+    else launch_prefill_split<128, 2>(G, grid, s, part_o, part_ml, q, k_cache, v_cache, block_tables, cu_seqlens_q,
+                                      seq_lens, hq, hkv, max_blocks, nsplit, split_chunks, sl2);
+  } else {
+    if (nt == 1) launch_prefill_split<64, 1>(G, grid, s, part_o, part_ml, q, k_cache, v_cache, block_tables,
+                                             cu_seqlens_q, seq_lens, hq, hkv, max_blocks, nsplit, split_chunks, sl2);
+    else launch_prefill_split<64, 2>(G, grid, s, part_o, part_ml, q, k_cache, v_cache, block_tables, cu_seqlens_q,
+                                     seq_lens, hq, hkv, max_blocks, nsplit, split_chunks, sl2);
+  }
+  DLLM_HIP_CHECK(hipGetLastError());
+  if (d == 128)
+    hipLaunchKernelGGL(attn_split_reduce_kernel<128>, dim3((unsigned)total_tokens * hq), dim3(128), 0, s, (bf16*)out,
+                       (const float*)part_o, (const float*)part_ml, nsplit);
+  else
+    hipLaunchKernelGGL(attn_split_reduce_kernel<64>, dim3((unsigned)total_tokens * hq), dim3(64), 0, s, (bf16*)out,
+                       (const float*)part_o, (const float*)part_ml, nsplit);
   DLLM_HIP_CHECK(hipGetLastError());
 }
 

@@ -89,6 +89,12 @@ void paged_attention_prefill(uintptr_t out, uintptr_t q, uintptr_t k_cache, uint
                              uintptr_t block_tables, uintptr_t cu_seqlens_q, uintptr_t seq_lens, int batch,
                              int hq, int hkv, int d, int block_size, int max_blocks, int max_q_len, float scale,
                              int version, uintptr_t positions, uintptr_t cos_sin, int q_stride, uintptr_t stream);
+// prefill version 5 (split context): partials [T, hq, nsplit, D] / [T, hq, nsplit, 2] floats + the split reduce
+void paged_attention_prefill_split(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
+                                   uintptr_t block_tables, uintptr_t cu_seqlens_q, uintptr_t seq_lens,
+                                   uintptr_t part_o, uintptr_t part_ml, int batch, int total_tokens, int hq, int hkv,
+                                   int d, int block_size, int max_blocks, int max_q_len, int max_ctx, int nsplit,
+                                   int split_chunks, float scale, uintptr_t stream);
 
 long p2p_inbox_bytes(long chunk, int nslots);
 void p2p_standin(uintptr_t src, uintptr_t s_inbox, long s_bytes, uint64_t s_seq0, uintptr_t dst, uintptr_t r_inbox,

@@ -13,9 +13,25 @@
 
 void register_block_manager(py::module_& m) {
   py::class_<BlockManager>(m, "BlockManager")
-      .def(py::init<int, int>(), py::arg("num_blocks"), py::arg("block_size"))
+      .def(py::init<int, int, bool>(), py::arg("num_blocks"), py::arg("block_size"),
+           py::arg("prefix_caching") = false)
       .def_property_readonly("num_blocks", &BlockManager::num_blocks)
       .def_property_readonly("block_size", &BlockManager::block_size)
+      .def_property_readonly("prefix_caching", &BlockManager::prefix_caching)
+      .def("num_evictable", &BlockManager::num_evictable)
+      .def("num_registered", &BlockManager::num_registered)
+      .def("prefix_keys", &BlockManager::prefix_keys, py::arg("tokens"), py::arg("nblocks") = -1)
+      .def("match_prefix", &BlockManager::match_prefix)
+      .def("acquire_prefix", &BlockManager::acquire_prefix, py::arg("seq"), py::arg("tokens"),
+           py::arg("count_query") = true)
+      .def("register_prefix", &BlockManager::register_prefix, py::arg("seq"), py::arg("tokens"),
+           py::arg("num_tokens"))
+      .def("ref_count", &BlockManager::ref_count)
+      .def("is_registered", &BlockManager::is_registered)
+      .def("evictable_blocks", &BlockManager::evictable_blocks)
+      .def("free_blocks", &BlockManager::free_blocks)
+      .def("prefix_stats", &BlockManager::prefix_stats)
+      .def("set_hash_mask", &BlockManager::set_hash_mask)
       .def("num_free", &BlockManager::num_free)
       .def("num_sequences", &BlockManager::num_sequences)
       .def("blocks_for", &BlockManager::blocks_for)

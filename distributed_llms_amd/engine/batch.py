@@ -343,4 +343,5 @@ def to_device_meta(hb: HostBatch, device, pad_ctx_to: Optional[int] = None) -> (
         meta.cu_seqlens_p = up(hb.cu_seqlens[nd:] - nd)
         meta.max_ctx_d = int(hb.seq_lens[:nd].max())
         meta.max_q_len_p = int((hb.cu_seqlens[nd + 1:] - hb.cu_seqlens[nd:-1]).max())
+        meta.max_ctx_p = int(hb.seq_lens[nd:].max())
     return ids, meta

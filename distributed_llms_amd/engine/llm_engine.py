@@ -31,8 +31,10 @@ from .sequence import SamplingParams, Sequence, request_seed, validate_logprobs,
 log = logging.getLogger("dllm.engine")
 
 
-def make_block_manager(num_blocks: int, block_size: int):
-    bm = _ext.runtime().BlockManager(num_blocks, block_size)
+def make_block_manager(num_blocks: int, block_size: int, prefix_caching: bool = False):
+    """``prefix_caching`` (EngineConfig.enable_prefix_caching): reference-counted, content-addressed
+    blocks (csrc/runtime/block_manager.h); off, the plain free list."""
+    bm = _ext.runtime().BlockManager(num_blocks, block_size, bool(prefix_caching))
     # block 0 is the scratch block padded decode rows write into
     assert bm.ensure_capacity(SCRATCH_SEQ_ID, 1)
     assert bm.block_table(SCRATCH_SEQ_ID) == [0]
@@ -71,9 +73,10 @@ class LLMEngine:
         self.tp = self.stage.tp if self.stage.tp.enabled else None
         if self.tp is not None:
             ecfg = self.ecfg = ecfg.apply_overrides(use_graphs=False, streams=1)
+            ecfg.check_tensor_parallel(self.tp.size)
         self.num_slots = max(1, ecfg.streams) if gpu else 1
         self.runner = StageRunner(self.stage, ecfg, num_slots=self.num_slots)
-        self.bm = make_block_manager(self.runner.num_blocks, ecfg.kv_block_size)
+        self.bm = make_block_manager(self.runner.num_blocks, ecfg.kv_block_size, ecfg.enable_prefix_caching)
         # max_batch is the engine's total decode batch, split evenly over the slots
         per_slot = -(-ecfg.max_batch // self.num_slots)
         self.scheduler = Scheduler(self.bm, self.num_slots, per_slot, ecfg.max_prefill_tokens, ecfg.max_seq_len,

@@ -136,6 +136,15 @@ class Scheduler:
         self._rows_held = 0
         self._issued = 0
         self._completed = 0
+        # automatic prefix caching (a BlockManager built with prefix_caching): admission first takes
+        # the longest registered prefix of a new sequence; full PROMPT blocks are registered when the
+        # step that computed them completes.  _pending: chained block keys that admitted prefills
+        # will register once they complete -> their sequence ids; a waiting sequence that would
+        # gain a block from one of them is passed over until the producer has left (same-burst sharing)
+        self.prefix = bool(getattr(block_manager, "prefix_caching", False))
+        self._pending: Dict[int, set] = {}
+        self._pending_of: Dict[int, List[int]] = {}
+        self.num_deferrals = 0
 
     # ------------------------------------------------------------ requests
     def add(self, seq: Sequence) -> None:
@@ -150,6 +159,7 @@ class Scheduler:
         for s in list(self.waiting):
             if s.seq_id == seq_id:
                 self.waiting.remove(s)
+                self._clear_pending(s)
                 self.bm.free_sequence(s.seq_id)       # a partly prefilled prompt holds blocks
                 self._release_row(s)
                 s.finish("abort")
@@ -180,6 +190,57 @@ class Scheduler:
             self._quarantine.append((self._issued, seq.state_row))
             seq.state_row = -1
             self._rows_held -= 1
+
+    # ------------------------------------------------------------ prefix cache
+    @staticmethod
+    def _prompt(seq: Sequence) -> np.ndarray:
+        """The prompt ids as the block manager takes them (converted once: a deferred sequence is
+        looked at again on every admission pass)."""
+        if seq.prompt_i32 is None:
+            seq.prompt_i32 = np.asarray(seq.prompt, dtype=np.int32)
+        return seq.prompt_i32
+
+    @classmethod
+    def _tokens(cls, seq: Sequence) -> np.ndarray:
+        p = cls._prompt(seq)
+        return np.concatenate([p, np.asarray(seq.output, dtype=np.int32)]) if seq.output else p
+
+    def _add_pending(self, seq: Sequence) -> None:
+        """The full prompt blocks ``seq`` will have registered when its prefill is through."""
+        if seq.seq_id in self._pending_of:
+            return
+        keys = self.bm.prefix_keys(self._prompt(seq), -1)
+        self._pending_of[seq.seq_id] = keys
+        for k in keys:
+            self._pending.setdefault(k, set()).add(seq.seq_id)
+
+    def _clear_pending(self, seq: Sequence) -> None:
+        for k in self._pending_of.pop(seq.seq_id, ()):
+            ids = self._pending.get(k)
+            if ids is not None:
+                ids.discard(seq.seq_id)
+                if not ids:
+                    del self._pending[k]
+
+    def _gains_by_waiting(self, toks: np.ndarray) -> bool:
+        """Whether a prefill in flight will register a block this sequence could share and cannot yet."""
+        if not self._pending:
+            return False
+        cap = (len(toks) - 1) // self.bm.block_size
+        have = self.bm.match_prefix(toks)
+        if have >= cap:
+            return False
+        return any(k in self._pending for k in self.bm.prefix_keys(toks, cap)[have:])
+
+    def _register_prompt(self, seq: Sequence) -> None:
+        n = min(seq.num_cached, len(seq.prompt))
+        if n >= self.bm.block_size:
+            self.bm.register_prefix(seq.seq_id, self._prompt(seq), n)
+
+    def prefix_stats(self) -> Dict[str, int]:
+        """Counters of the prefix cache (zeros with the cache off)."""
+        q, h, e, r = self.bm.prefix_stats()
+        return {"query_tokens": int(q), "hit_tokens": int(h), "evictions": int(e), "cached_blocks": int(r)}
 
     def _step(self, *args, **kw) -> Step:
         """A step about to be handed out (every one of them comes back through complete())."""
@@ -220,8 +281,19 @@ class Scheduler:
         tokens = 0
         target = self._admission_target()
         blocked = False
+        deferred: List[Sequence] = []       # passed over for a pending key; they keep their queue position
         while self.waiting and n_running + len(admitted) < target:
             seq = self.waiting[0]
+            if self.prefix and seq.num_cached == 0 and not self.bm.has_sequence(seq.seq_id):
+                toks = self._tokens(seq)
+                if self._gains_by_waiting(toks):
+                    deferred.append(self.waiting.popleft())
+                    self.num_deferrals += 1
+                    continue
+                # one query per admission in the counters, however many passes it takes
+                hit = int(self.bm.acquire_prefix(seq.seq_id, toks, not seq.prefix_queried))
+                seq.prefix_queried = True
+                seq.num_cached = seq.prefix_hit = hit
             n = seq.total_len - seq.num_cached
             budget = max_tokens - tokens
             if n > budget:
@@ -244,6 +316,12 @@ class Scheduler:
             seq.slot = slot
             admitted.append(seq)
             tokens += n
+            if self.prefix:
+                seq.cached_tokens += seq.prefix_hit
+                seq.prefix_hit = 0
+                seq.prefix_queried = False      # a re-admission after preemption is a new query
+                self._add_pending(seq)
+        self.waiting.extendleft(reversed(deferred))
         return admitted, blocked
 
     def schedule(self, slot: int = 0, _retry: bool = True) -> Optional[Step]:
@@ -297,14 +375,17 @@ class Scheduler:
         freed = False
         for s in list(self.waiting)[1:]:
             if s.num_cached > 0:
+                self._clear_pending(s)
                 self.bm.free_sequence(s.seq_id)
-                s.num_cached = 0
+                s.num_cached = s.prefix_hit = 0
+                s.prefix_queried = False
                 s.chunk = 0
                 freed = True
         if freed:
             return True
         # nothing else holds blocks: the pool cannot hold the head's next chunk at all
         self.waiting.popleft()
+        self._clear_pending(head)
         self.bm.free_sequence(head.seq_id)
         self._release_row(head)
         head.finish("kv_capacity")
@@ -325,6 +406,7 @@ class Scheduler:
     def _sync_preempted(self):
         for sid in self.native.take_preempted():
             seq = self.live.pop(int(sid))
+            self._clear_pending(seq)
             toks, times = self.native.take_output(sid)
             seq.output.extend(toks.tolist())
             seq.token_times.extend(times.tolist())
@@ -395,6 +477,7 @@ class Scheduler:
             st = seq.status
             if st is SeqStatus.FINISHED or st is SeqStatus.ABORTED:   # aborted while in flight
                 seq.chunk = 0
+                self._clear_pending(seq)
                 continue
             if seq.chunk:
                 # a non-final chunk: its KV is cached, its sampled token is meaningless; the rest of
@@ -403,8 +486,13 @@ class Scheduler:
                 seq.chunk = 0
                 seq.status = SeqStatus.WAITING
                 self.waiting.appendleft(seq)
+                if self.prefix:
+                    self._register_prompt(seq)      # the chunk's K/V are in the cache: this step completed
                 continue
             seq.num_cached = len(seq.prompt) + len(seq.output)
+            if self.prefix:
+                self._register_prompt(seq)
+                self._clear_pending(seq)
             if logprobs is not None and seq.params.logprobs is not None:
                 n = seq.params.logprobs
                 seq.logprobs.append((float(logprobs[0][i]), logprobs[1][i, :n].tolist(),

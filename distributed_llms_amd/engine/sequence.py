@@ -12,7 +12,7 @@ import itertools
 import math
 import time
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Any, Dict, List, Optional
 
 
 class SeqStatus(enum.Enum):
@@ -175,6 +175,16 @@ class Sequence:
     # requests with logit processors: their LogitState row, handed out by the Scheduler at admission,
     # kept through preemption, released at finish or abort (-1: none)
     state_row: int = -1
+    # prefix caching: tokens this sequence did not compute because their K/V blocks were found in the
+    # paged cache at admission (summed over re-admissions after preemption); prefix_hit: the hit of an
+    # acquisition whose first step has not been admitted yet
+    cached_tokens: int = 0
+    prefix_hit: int = 0
+    # prefix caching: whether this admission's query is in the cache's queried-tokens counter already
+    # (a sequence that found nothing and could not be admitted is looked up again on every pass), and
+    # the prompt ids as the int32 array the block manager takes (made once by the scheduler)
+    prefix_queried: bool = False
+    prompt_i32: Optional[Any] = field(default=None, repr=False, compare=False)
 
     def __post_init__(self):
         if not self.prompt:

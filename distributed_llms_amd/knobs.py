@@ -89,6 +89,14 @@ class Knobs:
     attn_target_waves: int = 1024     # decode split-KV: waves to aim for (profiles/attn_decode_sweep.txt)
     prefill_attn: int = 0             # prefill kernel: 0 = auto (9 from prefill_w32_min_q query rows at head_dim 128 -- 7 while comm kernels hold CUs -- else 4); 4 = LDS-shared K/V tiles on 16x16 MFMAs, 7 = the same on 32x32x16 MFMAs with P.V overlapping the softmax, 9 = 7 persistent (one workgroup per CU), 3 = register-tiled (> 32k fallback)
     prefill_w32_min_q: int = 384      # auto: the 32x32 kernel from this many query rows (128 x 256-token prompts: v4 209-215 us, v9 210-212; 96 x 384: 267-272 vs 260-262; profiles/round6_attention.md)
+    # split-context prefill (kernel 5; prefill_attn = 5 forces it): a prefill call whose plain grid cannot
+    # fill the device (ops.prefill_split_eligible: few sequences, at most 64 query rows each -- the tail of
+    # a prompt whose prefix was found in the paged cache; in pure prefill steps and in the prefill rows of
+    # mixed steps) takes it from this longest context on; 0 = never.
+    # Against v4 at Llama-3-8B heads (profiles/prefix_cache.md): B = 1 from 1.5x (1k context, 64 rows)
+    # to 19.9x (32k, 1 row); B = 8 loses at 64 rows below 4k (0.68x at 1k, 0.87x at 2k) and wins every
+    # eligible shape from 4k on (1.05x .. 5.2x, spread of a cell <= 2 %)
+    prefill_split_min_ctx: int = 4096
     # prefill q-RoPE in the attention kernel's q load (rope_cache appends K / V only): no rotated-q
     # round trip through HBM (268 MB per layer at T = 32768)
     prefill_fused_rope: bool = True

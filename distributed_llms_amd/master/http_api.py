@@ -26,6 +26,13 @@ dependency; every request thread only submits to the master's request futures):
                                OpenAI's string keys), "min_tokens" (no EOS before that many tokens).  They
                                rewrite the logits that greedy selection, sampling and "logprobs" then see;
                                a value out of range: 400
+  "n": k                       (either POST, 1..16, not with "stream") k completions per prompt, submitted as k
+                               plain requests: child j of a request with "seed" s samples with seed
+                               (s + j) mod 2^64, without a seed every child draws its own.  /v1/completions:
+                               choices[i * k + j] is child j of prompt i, "usage.prompt_tokens" counts each
+                               prompt once and "usage.prompt_tokens_details.cached_tokens" the prompt tokens
+                               found in the prefix cache (EngineConfig.enable_prefix_caching); /generate with
+                               k > 1: {"results": [the k replies]}.  Anything else: 400
   "stream": true               (either POST, one prompt) server-sent events: one ``data: {...}`` event
                                per pipeline step that produced tokens (TOKENS messages from stage 0),
                                then ``data: [DONE]`` (not together with "logprobs": 400)
@@ -61,6 +68,28 @@ def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_n
         raise ValueError("logprobs are not available with stream")
     validate_processors(p, vocab_size)       # logit_bias arrives with string keys: {int: float} from here on
     return p
+
+
+MAX_N = 16
+
+
+def _num_completions(body: Dict[str, Any]) -> int:
+    """The request's ``"n"``: an integer (not a bool) from 1 to MAX_N, not together with "stream"."""
+    n = body.get("n")
+    if n is None:
+        return 1
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_N:
+        raise ValueError(f"n must be an integer from 1 to {MAX_N}, got {n!r}")
+    if body.get("stream"):
+        raise ValueError("n is not available with stream")
+    return n
+
+
+def _child_params(params: Dict[str, Any], j: int) -> Dict[str, Any]:
+    """Child ``j`` of an ``n``-fold request: the same parameters, the seed moved on by j."""
+    if j == 0 or params.get("seed") is None:
+        return params
+    return dict(params, seed=(int(params["seed"]) + j) & ((1 << 64) - 1))
 
 
 def _finite(x: float):
@@ -152,6 +181,7 @@ class _Handler(BaseHTTPRequestHandler):
     def _stream(self, body: Dict[str, Any]):
         """Server-sent events: token chunks as stage 0 produces them, then [DONE]."""
         completions = self.path == "/v1/completions"
+        _num_completions(body)
         prompt = body["prompt_ids"] if "prompt_ids" in body else body.get("prompt", "")
         ids = self._ids(prompt)
         if not ids:
@@ -198,26 +228,33 @@ class _Handler(BaseHTTPRequestHandler):
             return list(prompt)
         raise ValueError("prompt must be a string or a list of token ids")
 
-    def _run(self, prompts: List[List[int]], params: Dict[str, Any]) -> List[Dict[str, Any]]:
+    def _run(self, prompts: List[List[int]], params: Dict[str, Any], n: int = 1) -> List[Dict[str, Any]]:
+        """``n`` results per prompt, prompt-major (result i * n + j: child j of prompt i)."""
         if not prompts or any(not p for p in prompts):
             raise ValueError("empty prompt")
         m = self.master
-        futs = [m.submit(p, params) for p in prompts]          # submitted together -> batched together
+        # submitted together -> batched together (the children of a prompt share its blocks
+        # through the prefix cache when the engines run with one)
+        futs = [m.submit(p, _child_params(params, j)) for p in prompts for j in range(n)]
         out = []
         for f in futs:
             r = m._finish(f, self.timeout_s)
             r["text"] = m.tokenizer.decode(r["tokens"])
             if r.get("logprobs") is None:
                 r.pop("logprobs", None)                # a request that did not ask: the reply it always got
+            if not r.get("cached_tokens"):
+                r.pop("cached_tokens", None)           # no hit (or no cache): likewise
             out.append(r)
         return out
 
     def _generate(self, body: Dict[str, Any]) -> Dict[str, Any]:
         ids = body["prompt_ids"] if "prompt_ids" in body else self._ids(body.get("prompt", ""))
-        r = self._run([self._ids(ids)], _sampling(body, vocab_size=self._vocab()))[0]
-        if "logprobs" in r:
-            r["logprobs"] = _generate_logprobs(r["logprobs"])
-        return r
+        n = _num_completions(body)
+        res = self._run([self._ids(ids)], _sampling(body, vocab_size=self._vocab()), n)
+        for r in res:
+            if "logprobs" in r:
+                r["logprobs"] = _generate_logprobs(r["logprobs"])
+        return res[0] if n == 1 else {"results": res}
 
     def _completions(self, body: Dict[str, Any]) -> Dict[str, Any]:
         prompt = body.get("prompt", "")
@@ -225,7 +262,8 @@ class _Handler(BaseHTTPRequestHandler):
             prompts = [self._ids(p) for p in prompt]           # a batch of prompts
         else:
             prompts = [self._ids(prompt)]
-        res = self._run(prompts, _sampling(body, default_max=16, max_key="max_tokens", vocab_size=self._vocab()))
+        n = _num_completions(body)
+        res = self._run(prompts, _sampling(body, default_max=16, max_key="max_tokens", vocab_size=self._vocab()), n)
         choices = [{"index": i, "text": r["text"], "tokens": r["tokens"],
                     "finish_reason": "length" if r.get("finish_reason") in ("length", "max_seq_len") else "stop"}
                    for i, r in enumerate(res)]
@@ -236,7 +274,9 @@ class _Handler(BaseHTTPRequestHandler):
         ctok = sum(len(r["tokens"]) for r in res)
         return {"id": res[0].get("task_id"), "object": "text_completion", "created": int(time.time()),
                 "model": self.master.model_spec, "choices": choices,
-                "usage": {"prompt_tokens": ptok, "completion_tokens": ctok, "total_tokens": ptok + ctok}}
+                "usage": {"prompt_tokens": ptok, "completion_tokens": ctok, "total_tokens": ptok + ctok,
+                          "prompt_tokens_details": {"cached_tokens": sum(int(r.get("cached_tokens") or 0)
+                                                                         for r in res)}}}
 
 
 def serve_http(master, host: str = "127.0.0.1", port: int = 8000,

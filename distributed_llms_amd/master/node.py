@@ -609,7 +609,8 @@ class MasterNode:
         lat = time.perf_counter() - fut.t_submit
         self.metrics.record(len(ids), lat, header.get("ttft_s"))
         return {"task_id": header.get("task_id"), "tokens": ids, "finish_reason": header.get("finish_reason"),
-                "latency_s": lat, "ttft_s": header.get("ttft_s"), "logprobs": header.get("logprobs")}
+                "latency_s": lat, "ttft_s": header.get("ttft_s"), "logprobs": header.get("logprobs"),
+                "cached_tokens": int(header.get("cached_tokens") or 0)}
 
     def run_inference(self, input_text, timeout: float = 60, max_new_tokens: int = 32, **params) -> Dict[str, Any]:
         """Text (tokenized on the master) or token ids -> generated ids (+ detokenized text)."""

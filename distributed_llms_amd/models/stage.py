@@ -54,6 +54,7 @@ class BatchMeta:
     cu_seqlens_p: Optional[torch.Tensor] = None
     max_ctx_d: int = 0
     max_q_len_p: int = 0
+    max_ctx_p: int = 0          # the prefill rows' longest context (the split-context kernel's eligibility)
 
 
 class KVCache:
@@ -316,7 +317,9 @@ class ModelStage:
                                                 workspace=meta.attn_workspace)
             return o.view(o.shape[0], self.q_size_local)
         if meta.is_prefill and not meta.num_decode and qkv.is_cuda and \
-                ops.prefill_rope_in_attention(meta.block_tables.shape[1]):
+                ops.prefill_rope_in_attention(meta.block_tables.shape[1],
+                                              (meta.seq_lens.shape[0], self.hkv, meta.max_q_len, meta.max_ctx,
+                                               self.hq // self.hkv)):
             ops.rope_cache_append(qkv, meta.positions, self.cos_sin, k_cache, v_cache, meta.slot_mapping,
                                   self.hq, self.hkv, cfg.head_dim, write_q=False)
             o = ops.paged_attention_prefill_rope(qkv, meta.positions, self.cos_sin, k_cache, v_cache,
@@ -333,11 +336,13 @@ class ModelStage:
             ops.paged_attention_decode(q[:nd], k_cache, v_cache, meta.block_tables[:nd], meta.seq_lens[:nd],
                                        self.scale, max_ctx=meta.max_ctx_d or None, out=o[:nd])
             ops.paged_attention_prefill(q[nd:], k_cache, v_cache, meta.block_tables[nd:], meta.cu_seqlens_p,
-                                        meta.seq_lens[nd:], self.scale, max_q_len=meta.max_q_len_p, out=o[nd:])
+                                        meta.seq_lens[nd:], self.scale, max_q_len=meta.max_q_len_p, out=o[nd:],
+                                        max_ctx=meta.max_ctx_p or None)
             return o.view(o.shape[0], self.q_size_local)
         if meta.is_prefill:
             o = ops.paged_attention_prefill(q, k_cache, v_cache, meta.block_tables, meta.cu_seqlens_q,
-                                            meta.seq_lens, self.scale, max_q_len=meta.max_q_len)
+                                            meta.seq_lens, self.scale, max_q_len=meta.max_q_len,
+                                            max_ctx=meta.max_ctx or None)
         else:
             o = ops.paged_attention_decode(q, k_cache, v_cache, meta.block_tables, meta.seq_lens, self.scale,
                                            max_ctx=meta.max_ctx or None, workspace=meta.attn_workspace)

@@ -25,7 +25,7 @@ __all__ = [
     "gelu_tanh", "rope_cache_append", "paged_attention_decode", "paged_attention_prefill",
     "argmax", "add_", "moe_route", "moe_mlp", "decode_split_plan", "paged_attention_decode_rope",
     "paged_attention_prefill_rope", "sample_rows", "token_logprobs", "logit_state_update",
-    "apply_logit_processors", "logit_state_count",
+    "apply_logit_processors", "logit_state_count", "prefill_split_plan", "prefill_split_eligible",
 ]
 
 
@@ -361,9 +361,92 @@ def prefill_attn_version(max_q_len: int, head_dim: int) -> int:
     return 7 if gemm._comm_cus else 9
 
 
+PREFILL_SPLIT = 5            # the split-context prefill kernel's version number
+PF_SPLIT_MIN_CHUNKS = 8      # KV chunks (of 32 keys) a split walks at least: its load pipeline needs a run
+PF_SPLIT_TARGET_WGS = 512    # workgroups to aim for: two per CU
+PF_SPLIT_MAX_PLAIN_WGS = 128  # the plain grid "cannot fill the device": at most half the CUs
+PF_SPLIT_MAX_Q = 64          # query rows per sequence up to which the cutover was measured (profiles/prefix_cache.md)
+
+
+def _prefill_plain_wgs(batch: int, num_kv_heads: int, max_q_len: int, group: int) -> int:
+    """Workgroups of the 16x16 prefill kernels' grid (launch_prefill: 4 waves x 2 tiles x 16/G rows)."""
+    rows_per_wg = 4 * max(1, 16 // group) * 2
+    return -(-max_q_len // rows_per_wg) * num_kv_heads * batch
+
+
+def prefill_split_plan(batch: int, num_kv_heads: int, max_q_len: int, max_ctx: int, group: int,
+                       block_size: int = 32) -> Tuple[int, int]:
+    """(nsplit, split_chunks) of the split-context prefill kernel, chosen as decode_split_plan chooses:
+    enough splits to fill the CUs (PF_SPLIT_TARGET_WGS workgroups over the kernel's own grid, which puts
+    one tile on a wave while the rows fit one workgroup), with a floor of PF_SPLIT_MIN_CHUNKS chunks per
+    split.  Split s covers the chunks [s, s + 1) x split_chunks of every sequence."""
+    rows1 = 4 * max(1, 16 // group)
+    rows_per_wg = rows1 if max_q_len <= rows1 else 2 * rows1
+    wgs = max(1, -(-max_q_len // rows_per_wg) * num_kv_heads * batch)
+    chunks = max(1, -(-max_ctx // block_size))
+    nsplit = max(1, min(-(-PF_SPLIT_TARGET_WGS // wgs), chunks // PF_SPLIT_MIN_CHUNKS))
+    split_chunks = -(-chunks // nsplit)
+    return -(-chunks // split_chunks), split_chunks
+
+
+def prefill_split_eligible(batch: int, num_kv_heads: int, max_q_len: int, max_ctx: Optional[int], group: int) -> bool:
+    """Whether a prefill call takes the split-context kernel by default: a short tail (at most
+    PF_SPLIT_MAX_Q query rows per sequence -- the range the cutover was measured in; longer chunks of a
+    chunked prompt keep the kernel they had), a plain grid that cannot fill the device (few sequences: at
+    most PF_SPLIT_MAX_PLAIN_WGS workgroups), a longest context that reaches knobs.prefill_split_min_ctx
+    (0: never) and a plan with more than one split.  The rule also bounds the partial workspace:
+    T <= 32 x PF_SPLIT_MAX_PLAIN_WGS rows."""
+    min_ctx = knobs.K.prefill_split_min_ctx
+    if not min_ctx or not max_ctx or max_ctx < min_ctx or knobs.K.prefill_attn != 0:
+        return False
+    if max_q_len > PF_SPLIT_MAX_Q:
+        return False
+    if group not in (1, 2, 4, 8, 16) or _prefill_plain_wgs(batch, num_kv_heads, max_q_len, group) > PF_SPLIT_MAX_PLAIN_WGS:
+        return False
+    return prefill_split_plan(batch, num_kv_heads, max_q_len, max_ctx, group)[0] > 1
+
+
+def _prefill_split(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, scale, max_q_len, max_ctx, out,
+                   nsplit: Optional[int], workspace: Optional[tuple]):
+    t, hq, d = q.shape
+    b = seq_lens.shape[0]
+    hkv, bs, max_blocks = k_cache.shape[1], k_cache.shape[2], block_tables.shape[1]
+    if max_ctx is None:
+        max_ctx = int(seq_lens.max().item()) if b else 0
+    if max_ctx > max_blocks * bs:
+        raise ValueError("max_ctx exceeds block table capacity")
+    chunks = max(1, -(-max_ctx // bs))
+    if nsplit is None:
+        nsplit, split_chunks = prefill_split_plan(b, hkv, int(max_q_len), max_ctx, hq // hkv, bs)
+    else:       # forced (tests, benchmarks): also more splits than chunks, the trailing ones empty
+        nsplit = int(nsplit)
+        if nsplit < 1:
+            raise ValueError("nsplit >= 1")
+        split_chunks = max(1, -(-chunks // nsplit))
+    if workspace is None:
+        po_t = torch.empty(t * hq * nsplit * d, dtype=torch.float32, device=q.device)
+        pml_t = torch.empty(t * hq * nsplit * 2, dtype=torch.float32, device=q.device)
+    else:
+        po_t, pml_t = workspace
+        if po_t.numel() < t * hq * nsplit * d or pml_t.numel() < t * hq * nsplit * 2:
+            raise ValueError("attention workspace too small")
+    _ext.kernels().paged_attention_prefill_split(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                                 block_tables.data_ptr(), cu_seqlens_q.data_ptr(), seq_lens.data_ptr(),
+                                                 po_t.data_ptr(), pml_t.data_ptr(), b, t, hq, hkv, d, bs, max_blocks,
+                                                 int(max_q_len), int(max_ctx), nsplit, split_chunks, float(scale),
+                                                 _stream())
+    return out
+
+
 def paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, scale: float,
-                            max_q_len: Optional[int] = None, version: int = 0, out: Optional[torch.Tensor] = None):
-    """``version``: prefill kernel 3, 4, 7 or 9 (0: prefill_attn_version); ``out`` as paged_attention_decode."""
+                            max_q_len: Optional[int] = None, version: int = 0, out: Optional[torch.Tensor] = None,
+                            max_ctx: Optional[int] = None, nsplit: Optional[int] = None,
+                            workspace: Optional[tuple] = None):
+    """``version``: prefill kernel 3, 4, 5, 7 or 9 (0: prefill_attn_version, or 5 where ``max_ctx`` -- the
+    batch's longest context, known to the host -- makes the call prefill_split_eligible); ``out`` as
+    paged_attention_decode.  Version 5 is the split-context kernel (every row of q must belong to a
+    sequence): ``nsplit`` forces its split count (None: prefill_split_plan), ``workspace`` its (o, ml)
+    partial buffers (None: allocated for the call)."""
     if not _gpu(q):
         return _into(out, ref.paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens,
                                                       scale))
@@ -381,9 +464,16 @@ def paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq
         out = torch.empty_like(q)
     elif out.shape != q.shape or not out.is_contiguous() or out.dtype != q.dtype:
         raise ValueError("attention out must be a contiguous tensor shaped like q")
+    hkv = k_cache.shape[1]
+    version = version or (PREFILL_SPLIT if knobs.K.prefill_attn == PREFILL_SPLIT else 0)
+    if version == PREFILL_SPLIT or (not version and prefill_split_eligible(b, hkv, int(max_q_len), max_ctx, hq // hkv)):
+        if t == 0 or b == 0:
+            return out
+        return _prefill_split(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, scale, max_q_len, max_ctx,
+                              out, nsplit, workspace)
     _ext.kernels().paged_attention_prefill(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                                            block_tables.data_ptr(), cu_seqlens_q.data_ptr(), seq_lens.data_ptr(),
-                                           b, hq, k_cache.shape[1], d, k_cache.shape[2], block_tables.shape[1],
+                                           b, hq, hkv, d, k_cache.shape[2], block_tables.shape[1],
                                            int(max_q_len), float(scale), version or prefill_attn_version(int(max_q_len), d),
                                            0, 0, 0,
                                            _stream())
@@ -393,12 +483,16 @@ def paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq
 PF_MAX_CHUNKS = 1024    # attention.hip kPfMaxChunks: the LDS prefill kernel stages <= 32k tokens of block ids
 
 
-def prefill_rope_in_attention(max_blocks: Optional[int] = None) -> bool:
+def prefill_rope_in_attention(max_blocks: Optional[int] = None, split_shape: Optional[tuple] = None) -> bool:
     """Prefill q-RoPE inside the attention kernel (knobs.prefill_fused_rope; LDS kernel versions).
     ``max_blocks``: the batch's block-table width -- beyond ``PF_MAX_CHUNKS`` (32k-token sequences)
     the launcher falls back to the register-tiled kernel, which reads a rotated q, so the caller
-    must take ``rope_cache_append(write_q=True)`` + the plain prefill kernel instead."""
+    must take ``rope_cache_append(write_q=True)`` + the plain prefill kernel instead.  The same
+    holds where the split-context kernel is chosen: ``split_shape`` = (batch, num_kv_heads, max_q_len,
+    max_ctx, group), the arguments of prefill_split_eligible."""
     if max_blocks is not None and max_blocks > PF_MAX_CHUNKS:
+        return False
+    if split_shape is not None and prefill_split_eligible(*split_shape):
         return False
     return knobs.K.prefill_fused_rope and knobs.K.prefill_attn in (0, 4, 7, 9)
 

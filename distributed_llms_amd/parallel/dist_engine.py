@@ -211,6 +211,7 @@ class RankRole:
     def __init__(self, ctx: DistContext, ecfg: EngineConfig, hf_state=None):
         self.ctx = ctx
         self.ecfg = ecfg
+        ecfg.check_tensor_parallel(ctx.tp)        # on every rank, before any of them builds a stage
         mcfg = ecfg.model_config()
         self.engine = None
         self.driver = None
@@ -244,7 +245,7 @@ class RankRole:
                                             timeout_s=ecfg.comm_timeout_s,
                                             max_ids=max_ids_message_len(ecfg.max_batch))
             if ctx.stage == 0 and ctx.tp_rank == 0:
-                bm = make_block_manager(nb, ecfg.kv_block_size)
+                bm = make_block_manager(nb, ecfg.kv_block_size, ecfg.enable_prefix_caching)
                 self.driver = PipelineDriver(self.runner, self.transport, ecfg, bm)
             elif ctx.stage == 0:
                 self.lane_follower = True

@@ -125,6 +125,8 @@ class PipelineDriver:
         self.lookahead = knobs.K.pp_lookahead
         # pp x tp: the stage-0 TP peers replay every issue on their own lanes
         self.tp = runner.stage.tp if runner.stage.tp.enabled else None
+        if self.tp is not None:
+            ecfg.check_tensor_parallel(self.tp.size)
         self._seed_rng = random.Random(os.urandom(16))     # seeds of sampled requests that bring none
         self.step_id = 0
         self.num_steps = 0
@@ -329,7 +331,7 @@ def run_loopback_pipeline(ecfg: EngineConfig, num_stages: int, prompts, params: 
     threads = [threading.Thread(target=follower, args=(s,), daemon=True) for s in range(1, num_stages)]
     for th in threads:
         th.start()
-    bm = make_block_manager(runners[0].num_blocks, ecfg.kv_block_size)
+    bm = make_block_manager(runners[0].num_blocks, ecfg.kv_block_size, ecfg.enable_prefix_caching)
     drv = PipelineDriver(runners[0], hub.transport(0), ecfg, bm)
     try:
         outs = drv.generate(prompts, params)

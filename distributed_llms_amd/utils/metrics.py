@@ -115,4 +115,13 @@ def cluster_prometheus_text(status: Dict, prefix: str = "dllm") -> str:
         if lines:
             out.append(f"# TYPE {prefix}_worker_{g} gauge")
             out += lines
+    # the prefix cache of every scheduling worker (stage 0 of each replica), summed; zeros with the cache off
+    pc = {k: 0 for k in ("query_tokens", "hit_tokens", "evictions", "cached_blocks")}
+    for w in (status.get("workers") or {}).values():
+        for k, v in (((w.get("remote") or {}).get("prefix_cache")) or {}).items():
+            if k in pc and isinstance(v, (int, float)):
+                pc[k] += int(v)
+    for k in ("query_tokens", "hit_tokens", "evictions"):
+        out += [f"# TYPE {prefix}_prefix_cache_{k}_total counter", f"{prefix}_prefix_cache_{k}_total {pc[k]}"]
+    out += [f"# TYPE {prefix}_prefix_cache_blocks gauge", f"{prefix}_prefix_cache_blocks {pc['cached_blocks']}"]
     return "\n".join(x for x in out if x) + "\n"

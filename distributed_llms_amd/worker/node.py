@@ -459,7 +459,7 @@ class WorkerNode:
                                        max_ids=max_ids_message_len(ecfg.max_batch))
             self._transport = transport
             if stage_idx == 0:
-                bm = make_block_manager(nb, ecfg.kv_block_size)
+                bm = make_block_manager(nb, ecfg.kv_block_size, ecfg.enable_prefix_caching)
                 self.driver = PipelineDriver(self.stage_runner, transport, ecfg, bm)
                 self.role = "driver"
                 self._serve_thread = self._spawn(self._serve_loop)
@@ -573,7 +573,8 @@ class WorkerNode:
                 if sock is None:
                     continue
                 meta = {"task_id": s.request_id, "finish_reason": s.finish_reason, "num_tokens": len(s.output),
-                        "ttft_s": s.ttft(), "latency_s": s.latency(), "prompt_tokens": len(s.prompt)}
+                        "ttft_s": s.ttft(), "latency_s": s.latency(), "prompt_tokens": len(s.prompt),
+                        "cached_tokens": min(s.cached_tokens, len(s.prompt))}
                 n_lp = s.params.logprobs
                 if n_lp is not None:      # the values ride in the payload behind the ids; the count here
                     meta["logprobs"] = n_lp
@@ -654,4 +655,5 @@ class WorkerNode:
             st["running"] = t.scheduler.num_running()
             st["waiting"] = len(t.scheduler.waiting)
             st["kv_free_blocks"] = t.bm.num_free()
+            st["prefix_cache"] = t.scheduler.prefix_stats()
         return st

@@ -11,6 +11,8 @@
 // column, the row max needs 2 cross-lane shuffles, and the lane's 8 probabilities are
 // exactly its B-operand fragment for O^T += V^T P^T (the k-order of the PV product is
 // permuted to match, so P never leaves the lane).  Online softmax in base 2.
+#include <type_traits>
+
 #include "common.h"
 #include "launchers.h"
 
@@ -1375,6 +1377,29 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32p_kernel(
 }
 
 // ------------------------------------------------------------------ launchers
+// f(std::integral_constant<int, V>{}) for the one V of Vs that equals v: a runtime value picks a template argument
+template <int... Vs, typename F>
+static void dispatch_value(int v, const char* what, F&& f) {
+  if (!((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...)) throw std::runtime_error(what);
+}
+
+// the GQA group sizes the prefill kernels are built for
+template <typename F>
+static void dispatch_group(int g, F&& f) {
+  dispatch_value<1, 2, 4, 8, 16>(g, "prefill attention: GQA group must be 1,2,4,8,16", f);
+}
+
+// out[rows, d] bf16 from the split kernels' partials (decode: rows = B * hq; prefill version 5: T * hq)
+static void launch_split_reduce(int d, unsigned rows, hipStream_t s, uintptr_t out, uintptr_t part_o, uintptr_t part_ml,
+                                int nsplit) {
+  dispatch_value<128, 64>(d, "head_dim must be 64 or 128", [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    hipLaunchKernelGGL(attn_split_reduce_kernel<D>, dim3(rows), dim3(D), 0, s, (bf16*)out, (const float*)part_o,
+                       (const float*)part_ml, nsplit);
+  });
+  DLLM_HIP_CHECK(hipGetLastError());
+}
+
 static void decode_launch(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t block_tables,
                           uintptr_t seq_lens, uintptr_t part_o, uintptr_t part_ml, int batch, int hq, int hkv, int d,
                           int block_size, int max_blocks, int num_splits, int split_len, float scale, RopeArgs ra,
@@ -1399,12 +1424,10 @@ static void decode_launch(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr
                        (const int32_t*)block_tables, (const int32_t*)seq_lens, (float*)part_o, (float*)part_ml, hq,
                        hkv, max_blocks, split_len, sl2, ra);
   };
-#define DLLM_DEC(DD, FF, PP)                                          \
-  do {                                                                \
-    if (wpb == 4) go(attn_decode_kernel<DD, 4, FF, PP>, 256);         \
-    else if (wpb == 2) go(attn_decode_kernel<DD, 2, FF, PP>, 128);    \
-    else go(attn_decode_kernel<DD, 1, FF, PP>, 64);                   \
-  } while (0)
+#define DLLM_DEC(DD, FF, PP)                                                            \
+  dispatch_value<4, 2, 1>(wpb, "decode attention: waves per workgroup", [&](auto w) {   \
+    go(attn_decode_kernel<DD, decltype(w)::value, FF, PP>, 64 * decltype(w)::value);    \
+  })
   const bool parts = fused && ra.part != nullptr;
   if (d == 128) {
     if (parts) {
@@ -1419,15 +1442,7 @@ static void decode_launch(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr
   }
 #undef DLLM_DEC
   DLLM_HIP_CHECK(hipGetLastError());
-  if (num_splits > 1) {
-    if (d == 128)
-      hipLaunchKernelGGL(attn_split_reduce_kernel<128>, dim3(batch * hq), dim3(128), 0, s, (bf16*)out,
-                         (const float*)part_o, (const float*)part_ml, num_splits);
-    else
-      hipLaunchKernelGGL(attn_split_reduce_kernel<64>, dim3(batch * hq), dim3(64), 0, s, (bf16*)out,
-                         (const float*)part_o, (const float*)part_ml, num_splits);
-    DLLM_HIP_CHECK(hipGetLastError());
-  }
+  if (num_splits > 1) launch_split_reduce(d, batch * hq, s, out, part_o, part_ml, num_splits);
 }
 
 void paged_attention_decode(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
@@ -1450,13 +1465,32 @@ void paged_attention_decode_rope(uintptr_t out, uintptr_t qkv, uintptr_t positio
                 max_blocks, num_splits, split_len, scale, ra, true, stream);
 }
 
-template <int D>
-static void launch_prefill(int g, int version, int max_q_len, int batch, int hkv, hipStream_t s, uintptr_t out,
-                           uintptr_t q, uintptr_t k_cache, uintptr_t v_cache, uintptr_t bt, uintptr_t cu, uintptr_t sl,
-                           int hq, int max_blocks, float sl2, uintptr_t pos, uintptr_t cs, int q_stride) {
-  // version 3: the register-tiled kernel, two tiles per wave; 4: the LDS-shared kernel, two tiles per
-  // wave; 7: the LDS-shared kernel on 32x32x16 MFMAs, 8 waves x 32 columns (head_dim 128), the previous
-  // tile's P.V overlapping this tile's softmax; 9: 7 persistent (one workgroup per CU)
+// positions / cos_sin / q_stride: q is the raw qkv projection (row stride q_stride elements) and RoPE
+// is applied in the kernel (the LDS kernels: versions 4, 7 and 9); cos_sin = 0: q is [T, hq, D], rotated
+void paged_attention_prefill(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
+                             uintptr_t block_tables, uintptr_t cu_seqlens_q, uintptr_t seq_lens, int batch,
+                             int hq, int hkv, int d, int block_size, int max_blocks, int max_q_len, float scale,
+                             int version, uintptr_t positions, uintptr_t cos_sin, int q_stride, uintptr_t stream) {
+  DLLM_HOST_CHECK(block_size == kBS, "paged attention requires block_size 32");
+  if (q_stride == 0) q_stride = hq * d;
+  DLLM_HOST_CHECK(q_stride >= hq * d && q_stride % 8 == 0, "q row stride");
+  DLLM_HOST_CHECK(cos_sin == 0 || positions != 0, "in-kernel RoPE needs positions");
+  DLLM_HOST_CHECK(d == 64 || d == 128, "head_dim must be 64 or 128");
+  DLLM_HOST_CHECK(hq % hkv == 0, "Hq % Hkv");
+  if (batch == 0 || max_q_len == 0) return;
+  const int g = hq / hkv;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const float sl2 = scale * 1.4426950408889634f;
+  // version: the kernel ops.prefill_route chose, run as given.  3: the register-tiled kernel, two tiles per
+  // wave, which also serves block tables wider than the 32k tokens of block ids the LDS kernels stage; 4:
+  // the LDS-shared kernel, two tiles per wave (short prompts); 7: the LDS-shared kernel on 32x32x16 MFMAs, 8
+  // waves x 32 columns (head_dim 128), the previous tile's P.V overlapping this tile's softmax; 9: 7
+  // persistent (one workgroup per CU; the default from 384 query rows, profiles/round6_attention.md)
+  DLLM_HOST_CHECK(version == 3 || version == 4 || version == 7 || version == 9,
+                  "prefill attention version 3, 4, 7 or 9");
+  DLLM_HOST_CHECK(version < 7 || (d == 128 && g <= 16), "prefill attention 7 / 9: head_dim 128, GQA group <= 16");
+  DLLM_HOST_CHECK(version == 3 || max_blocks <= kPfMaxChunks, "prefill attention 4 / 7 / 9: block tables <= 32k tokens");
+  DLLM_HOST_CHECK(q_stride == hq * d || version != 3, "in-kernel RoPE / strided q: LDS kernels only (<= 32k context)");
   const int nt = 2;
   const int rows_per_wg = version >= 7 ? kW32Waves * (32 / g) : kWaves * (16 / g) * nt;
   const dim3 grid((max_q_len + rows_per_wg - 1) / rows_per_wg, hkv, batch);
@@ -1472,85 +1506,26 @@ static void launch_prefill(int g, int version, int max_q_len, int batch, int hkv
   // the LDS kernels (4, 7, 9) share one signature; 9 appends its row-tile and group counts
   auto go = [&](auto kern, dim3 gr, int threads, auto... tail) {
     hipLaunchKernelGGL(kern, gr, dim3(threads), 0, s, (bf16*)out, (const bf16*)q, (const bf16*)k_cache,
-                       (const bf16*)v_cache, (const int32_t*)bt, (const int32_t*)cu, (const int32_t*)sl, hq, hkv,
-                       max_blocks, sl2, (const int32_t*)pos, (const float*)cs, q_stride, tail...);
+                       (const bf16*)v_cache, (const int32_t*)block_tables, (const int32_t*)cu_seqlens_q,
+                       (const int32_t*)seq_lens, hq, hkv, max_blocks, sl2, (const int32_t*)positions,
+                       (const float*)cos_sin, q_stride, tail...);
   };
-#define DLLM_PF(GG)                                                                                          \
-  do {                                                                                                       \
-    if (version == 9) {                                                                                      \
-      if constexpr (D == 128) go(attn_prefill_w32p_kernel<GG>, dim3(cus), kW32Waves * 64, (int)grid.x, batch * hkv); \
-    } else if (version == 7) {                                                                               \
-      if constexpr (D == 128) go(attn_prefill_w32_kernel<GG>, grid, kW32Waves * 64);                         \
-    } else if (version == 4)                                                                                 \
-      go(attn_prefill_lds_kernel<D, GG, 2>, grid, kWaves * 64);                                              \
-    else                                                                                                     \
-      hipLaunchKernelGGL((attn_prefill2_kernel<D, GG, 2>), grid, dim3(kWaves * 64), 0, s, (bf16*)out, (const bf16*)q, \
-                         (const bf16*)k_cache, (const bf16*)v_cache, (const int32_t*)bt, (const int32_t*)cu, \
-                         (const int32_t*)sl, hq, hkv, max_blocks, sl2);                                      \
-  } while (0)
-  switch (g) {
-    case 1: DLLM_PF(1); break;
-    case 2: DLLM_PF(2); break;
-    case 4: DLLM_PF(4); break;
-    case 8: DLLM_PF(8); break;
-    case 16: DLLM_PF(16); break;
-    default: throw std::runtime_error("prefill attention: GQA group must be 1,2,4,8,16");
-  }
-#undef DLLM_PF
-}
-
-// positions / cos_sin / q_stride: q is the raw qkv projection (row stride q_stride elements) and RoPE
-// is applied in the kernel (the LDS kernels: versions 4, 7 and 9); cos_sin = 0: q is [T, hq, D], rotated
-void paged_attention_prefill(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
-                             uintptr_t block_tables, uintptr_t cu_seqlens_q, uintptr_t seq_lens, int batch,
-                             int hq, int hkv, int d, int block_size, int max_blocks, int max_q_len, float scale,
-                             int version, uintptr_t positions, uintptr_t cos_sin, int q_stride, uintptr_t stream) {
-  DLLM_HOST_CHECK(block_size == kBS, "paged attention requires block_size 32");
-  if (q_stride == 0) q_stride = hq * d;
-  DLLM_HOST_CHECK(q_stride >= hq * d && q_stride % 8 == 0, "q row stride");
-  DLLM_HOST_CHECK(cos_sin == 0 || positions != 0, "in-kernel RoPE needs positions");
-  DLLM_HOST_CHECK(d == 64 || d == 128, "head_dim must be 64 or 128");
-  DLLM_HOST_CHECK(hq % hkv == 0, "Hq % Hkv");
-  if (batch == 0 || max_q_len == 0) return;
-  const int G = hq / hkv;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const float sl2 = scale * 1.4426950408889634f;
-  // version (ops.prefill_attn_version): 4 = the LDS-shared kernel (short prompts); 7 / 9 = the
-  // 32x32x16 kernels (9, persistent, by default from 384 query rows; profiles/round6_attention.md);
-  // 3 = the register-tiled kernel, which also serves block tables wider than the 32k tokens of
-  // block ids the LDS kernels stage
-  DLLM_HOST_CHECK(version == 3 || version == 4 || version == 7 || version == 9,
-                  "prefill attention version 3, 4, 7 or 9");
-  if (version >= 7 && (d != 128 || G > 16)) version = 4;           // the 32x32 kernels: head_dim 128, G | 32
-  if (version != 3 && max_blocks > kPfMaxChunks) version = 3;
-  DLLM_HOST_CHECK(q_stride == hq * d || version != 3, "in-kernel RoPE / strided q: LDS kernels only (<= 32k context)");
-  if (d == 128)
-    launch_prefill<128>(G, version, max_q_len, batch, hkv, s, out, q, k_cache, v_cache, block_tables, cu_seqlens_q,
-                        seq_lens, hq, max_blocks, sl2, positions, cos_sin, q_stride);
-  else
-    launch_prefill<64>(G, version, max_q_len, batch, hkv, s, out, q, k_cache, v_cache, block_tables, cu_seqlens_q,
-                       seq_lens, hq, max_blocks, sl2, positions, cos_sin, q_stride);
+  dispatch_value<128, 64>(d, "head_dim must be 64 or 128", [&](auto dc) {
+    dispatch_group(g, [&](auto gc) {
+      constexpr int D = decltype(dc)::value, G = decltype(gc)::value;
+      if (version == 9) {
+        if constexpr (D == 128) go(attn_prefill_w32p_kernel<G>, dim3(cus), kW32Waves * 64, (int)grid.x, batch * hkv);
+      } else if (version == 7) {
+        if constexpr (D == 128) go(attn_prefill_w32_kernel<G>, grid, kW32Waves * 64);
+      } else if (version == 4)
+        go(attn_prefill_lds_kernel<D, G, 2>, grid, kWaves * 64);
+      else
+        hipLaunchKernelGGL((attn_prefill2_kernel<D, G, 2>), grid, dim3(kWaves * 64), 0, s, (bf16*)out, (const bf16*)q,
+                           (const bf16*)k_cache, (const bf16*)v_cache, (const int32_t*)block_tables,
+                           (const int32_t*)cu_seqlens_q, (const int32_t*)seq_lens, hq, hkv, max_blocks, sl2);
+    });
+  });
   DLLM_HIP_CHECK(hipGetLastError());
-}
-
-template <int D, int NT>
-static void launch_prefill_split(int g, dim3 grid, hipStream_t s, uintptr_t part_o, uintptr_t part_ml, uintptr_t q,
-                                 uintptr_t k_cache, uintptr_t v_cache, uintptr_t bt, uintptr_t cu, uintptr_t sl, int hq,
-                                 int hkv, int max_blocks, int nsplit, int split_chunks, float sl2) {
-#define DLLM_PFS(GG)                                                                                              \
-  hipLaunchKernelGGL((attn_prefill_split_kernel<D, GG, NT>), grid, dim3(kWaves * 64), 0, s, (float*)part_o,       \
-                     (float*)part_ml, (const bf16*)q, (const bf16*)k_cache, (const bf16*)v_cache,                 \
-                     (const int32_t*)bt, (const int32_t*)cu, (const int32_t*)sl, hq, hkv, max_blocks, nsplit,     \
-                     split_chunks, sl2)
-  switch (g) {
-    case 1: DLLM_PFS(1); break;
-    case 2: DLLM_PFS(2); break;
-    case 4: DLLM_PFS(4); break;
-    case 8: DLLM_PFS(8); break;
-    case 16: DLLM_PFS(16); break;
-    default: throw std::runtime_error("prefill attention: GQA group must be 1,2,4,8,16");
-  }
-#undef DLLM_PFS
 }
 
 // Prefill version 5: q [T, hq, D] rotated, the context in the paged cache; part_o [T, hq, nsplit, D] and
@@ -1577,25 +1552,19 @@ void paged_attention_prefill_split(uintptr_t out, uintptr_t q, uintptr_t k_cache
   const int nt = max_q_len <= kWaves * (16 / G) ? 1 : 2;
   const int rows_per_wg = kWaves * (16 / G) * nt;
   const dim3 grid((unsigned)((max_q_len + rows_per_wg - 1) / rows_per_wg) * nsplit, hkv, batch);
-  if (d == 128) {
-    if (nt == 1) launch_prefill_split<128, 1>(G, grid, s, part_o, part_ml, q, k_cache, v_cache, block_tables,
-                                              cu_seqlens_q, seq_lens, hq, hkv, max_blocks, nsplit, split_chunks, sl2);
-    else launch_prefill_split<128, 2>(G, grid, s, part_o, part_ml, q, k_cache, v_cache, block_tables, cu_seqlens_q,
-                                      seq_lens, hq, hkv, max_blocks, nsplit, split_chunks, sl2);
-  } else {
-    if (nt == 1) launch_prefill_split<64, 1>(G, grid, s, part_o, part_ml, q, k_cache, v_cache, block_tables,
-                                             cu_seqlens_q, seq_lens, hq, hkv, max_blocks, nsplit, split_chunks, sl2);
-    else launch_prefill_split<64, 2>(G, grid, s, part_o, part_ml, q, k_cache, v_cache, block_tables, cu_seqlens_q,
-                                     seq_lens, hq, hkv, max_blocks, nsplit, split_chunks, sl2);
-  }
+  dispatch_value<128, 64>(d, "head_dim must be 64 or 128", [&](auto dc) {
+    dispatch_value<1, 2>(nt, "split prefill: tiles per wave", [&](auto ntc) {
+      dispatch_group(G, [&](auto gc) {
+        hipLaunchKernelGGL((attn_prefill_split_kernel<decltype(dc)::value, decltype(gc)::value, decltype(ntc)::value>),
+                           grid, dim3(kWaves * 64), 0, s, (float*)part_o, (float*)part_ml, (const bf16*)q,
+                           (const bf16*)k_cache, (const bf16*)v_cache, (const int32_t*)block_tables,
+                           (const int32_t*)cu_seqlens_q, (const int32_t*)seq_lens, hq, hkv, max_blocks, nsplit,
+                           split_chunks, sl2);
+      });
+    });
+  });
   DLLM_HIP_CHECK(hipGetLastError());
-  if (d == 128)
-    hipLaunchKernelGGL(attn_split_reduce_kernel<128>, dim3((unsigned)total_tokens * hq), dim3(128), 0, s, (bf16*)out,
-                       (const float*)part_o, (const float*)part_ml, nsplit);
-  else
-    hipLaunchKernelGGL(attn_split_reduce_kernel<64>, dim3((unsigned)total_tokens * hq), dim3(64), 0, s, (bf16*)out,
-                       (const float*)part_o, (const float*)part_ml, nsplit);
-  DLLM_HIP_CHECK(hipGetLastError());
+  launch_split_reduce(d, (unsigned)total_tokens * hq, s, out, part_o, part_ml, nsplit);
 }
 
 }  // namespace dllm

@@ -13,6 +13,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
+from .. import ops
 from ..models.stage import BatchMeta, ModelStage
 from .batch import HostBatch, next_pow2
 
@@ -45,9 +46,7 @@ class DecodeGraphRunner:
         self.seq_lens.fill_(1)
         self.block_tables = self.dev_in[4 * mb:].view(mb, max_blocks)
         self.hidden = None if stage.is_first else torch.zeros(mb, stage.in_width, dtype=stage.dtype, device=dev)
-        max_splits = 64
-        self.ws = (torch.empty(mb * cfg.num_heads * max_splits * cfg.head_dim, dtype=torch.float32, device=dev),
-                   torch.empty(mb * cfg.num_heads * max_splits * 2, dtype=torch.float32, device=dev))
+        self.ws = ops.decode_workspace(mb, cfg.num_heads, cfg.head_dim, dev)
         self.pinned = torch.empty(4 * mb + mb * max_blocks, dtype=torch.int32).pin_memory()
         self.pinned_np = self.pinned.numpy()
         self.graphs: Dict[Tuple[int, int], Tuple[torch.cuda.CUDAGraph, torch.Tensor]] = {}

@@ -316,15 +316,19 @@ class ModelStage:
                                                 cfg.head_dim, self.scale, max_ctx=meta.max_ctx or None,
                                                 workspace=meta.attn_workspace)
             return o.view(o.shape[0], self.q_size_local)
-        if meta.is_prefill and not meta.num_decode and qkv.is_cuda and \
-                ops.prefill_rope_in_attention(meta.block_tables.shape[1],
-                                              (meta.seq_lens.shape[0], self.hkv, meta.max_q_len, meta.max_ctx,
-                                               self.hq // self.hkv)):
+        route = None
+        if meta.is_prefill:      # asked per call: the knobs may differ between two runs of one host batch
+            nd = meta.num_decode     # a mixed step: the route of its prefill rows, which follow the decode rows
+            route = ops.prefill_route(meta.seq_lens.shape[0] - nd, self.hq, self.hkv, cfg.head_dim,
+                                      meta.max_q_len_p if nd else meta.max_q_len,
+                                      (meta.max_ctx_p if nd else meta.max_ctx) or None, meta.block_tables.shape[1],
+                                      allow_rope_in_kernel=not nd and qkv.is_cuda)
+        if route is not None and route.rope_in_kernel:
             ops.rope_cache_append(qkv, meta.positions, self.cos_sin, k_cache, v_cache, meta.slot_mapping,
                                   self.hq, self.hkv, cfg.head_dim, write_q=False)
             o = ops.paged_attention_prefill_rope(qkv, meta.positions, self.cos_sin, k_cache, v_cache,
                                                  meta.block_tables, meta.cu_seqlens_q, meta.seq_lens, self.hq,
-                                                 cfg.head_dim, self.scale, max_q_len=meta.max_q_len)
+                                                 cfg.head_dim, self.scale, max_q_len=meta.max_q_len, route=route)
             return o.view(o.shape[0], self.q_size_local)
         q = ops.rope_cache_append(qkv, meta.positions, self.cos_sin, k_cache, v_cache, meta.slot_mapping,
                                   self.hq, self.hkv, cfg.head_dim)
@@ -337,12 +341,12 @@ class ModelStage:
                                        self.scale, max_ctx=meta.max_ctx_d or None, out=o[:nd])
             ops.paged_attention_prefill(q[nd:], k_cache, v_cache, meta.block_tables[nd:], meta.cu_seqlens_p,
                                         meta.seq_lens[nd:], self.scale, max_q_len=meta.max_q_len_p, out=o[nd:],
-                                        max_ctx=meta.max_ctx_p or None)
+                                        max_ctx=meta.max_ctx_p or None, route=route)
             return o.view(o.shape[0], self.q_size_local)
         if meta.is_prefill:
             o = ops.paged_attention_prefill(q, k_cache, v_cache, meta.block_tables, meta.cu_seqlens_q,
                                             meta.seq_lens, self.scale, max_q_len=meta.max_q_len,
-                                            max_ctx=meta.max_ctx or None)
+                                            max_ctx=meta.max_ctx or None, route=route)
         else:
             o = ops.paged_attention_decode(q, k_cache, v_cache, meta.block_tables, meta.seq_lens, self.scale,
                                            max_ctx=meta.max_ctx or None, workspace=meta.attn_workspace)

@@ -152,7 +152,6 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
     if isinstance(w_gate_up, quant.Fp8Weight):
         return quant.linear_fp8(x, w_gate_up, swiglu=True)
     if _gpu(x):
-        from . import gemm
         y = gemm.linear_swiglu(x, w_gate_up)
         if y is not None:
             return y
@@ -183,358 +182,13 @@ def silu_mul(gu: torch.Tensor) -> torch.Tensor:
     return out
 
 
-# ----------------------------------------------------------- K4 + K5
-def rope_cache_append(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, num_heads, num_kv_heads,
-                      head_dim, write_q: bool = True) -> Optional[torch.Tensor]:
-    """Rotate k (and q) and append k / v^T to the paged cache; returns the rotated q [T, Hq, D], or
-    None with ``write_q=False`` (the prefill attention then rotates q itself)."""
-    if not _gpu(qkv):
-        q = ref.rope_cache_append(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, num_heads,
-                                  num_kv_heads, head_dim)
-        return q if write_q else None
-    _ck(qkv, "rope.qkv")
-    _ck(k_cache, "k_cache")
-    _ck(v_cache, "v_cache")
-    _ck(positions, "positions", torch.int32)
-    _ck(slot_mapping, "slot_mapping", torch.int32)
-    t = qkv.shape[0]
-    if qkv.shape[1] != (num_heads + 2 * num_kv_heads) * head_dim:
-        raise ValueError("qkv width mismatch")
-    if cos_sin is not None:
-        _ck(cos_sin, "cos_sin", torch.float32)
-        if cos_sin.shape[1] != head_dim:
-            raise ValueError("cos_sin width must equal head_dim")
-    q = torch.empty(t, num_heads, head_dim, dtype=qkv.dtype, device=qkv.device) if write_q else None
-    _ext.kernels().rope_cache_append(q.data_ptr() if write_q else 0, qkv.data_ptr(), positions.data_ptr(),
-                                     0 if cos_sin is None else cos_sin.data_ptr(), k_cache.data_ptr(),
-                                     v_cache.data_ptr(), slot_mapping.data_ptr(), t, num_heads, num_kv_heads,
-                                     head_dim, k_cache.shape[2], int(knobs.K.v_group_append), _stream())
-    return q
-
-
-# ---------------------------------------------------------- K6 / K7
-
-
-def decode_split_plan(batch: int, num_kv_heads: int, max_ctx: int, block_size: int = 32,
-                      max_blocks: Optional[int] = None, target_waves: Optional[int] = None) -> Tuple[int, int]:
-    """(num_splits, split_len) for the decode kernel (one wave per split x kv-head x sequence).
-
-    Aim for ~8 waves per CU (256 CUs) with >= 2 KV blocks per split so each wave's load
-    pipeline has something to overlap.  The split BOUNDARIES depend only on the pow2-bucketed
-    batch x kv-heads and on the block-table width -- not on ``max_ctx`` -- so a graph replayed
-    at a padded (batch, context) bucket and the eager path partition every sequence's keys
-    identically: the extra splits of the bucket are empty and add exact zeros, and the two
-    paths produce bit-identical attention.
-    """
-    target_waves = target_waves or knobs.K.attn_target_waves     # sweep: profiles/attn_decode_sweep.txt
-    max_blocks = max_blocks or -(-max_ctx // block_size)
-    pairs = 1 << max(0, (max(1, batch * num_kv_heads) - 1).bit_length())
-    target = max(1, min(64, target_waves // pairs))
-    split_len = block_size * max(2, -(-max_blocks // target))
-    splits = max(1, -(-max_ctx // split_len))
-    return splits, split_len
-
-
-def _into(out: Optional[torch.Tensor], y: torch.Tensor) -> torch.Tensor:
-    if out is None:
-        return y
-    out.copy_(y)
-    return out
-
-
-def paged_attention_decode(q, k_cache, v_cache, block_tables, seq_lens, scale: float,
-                           max_ctx: Optional[int] = None, workspace: Optional[tuple] = None,
-                           out: Optional[torch.Tensor] = None):
-    """``out``: write the result there (a contiguous [B, Hq, D] view, e.g. rows of a mixed step)."""
-    if not _gpu(q):
-        return _into(out, ref.paged_attention_decode(q, k_cache, v_cache, block_tables, seq_lens, scale))
-    _ck(q, "attn.q")
-    _ck(k_cache, "k_cache")
-    _ck(v_cache, "v_cache")
-    _ck(block_tables, "block_tables", torch.int32)
-    _ck(seq_lens, "seq_lens", torch.int32)
-    b, hq, d = q.shape
-    hkv, bs = k_cache.shape[1], k_cache.shape[2]
-    max_blocks = block_tables.shape[1]
-    if max_ctx is None:
-        max_ctx = max_blocks * bs
-    if max_ctx > max_blocks * bs:
-        raise ValueError("max_ctx exceeds block table capacity")
-    splits, split_len = decode_split_plan(b, hkv, max_ctx, bs, max_blocks)
-    if out is None:
-        out = torch.empty_like(q)
-    elif out.shape != q.shape or not out.is_contiguous() or out.dtype != q.dtype:
-        raise ValueError("attention out must be a contiguous tensor shaped like q")
-    po = pml = 0
-    if splits > 1:
-        if workspace is None:
-            po_t = torch.empty(b * hq * splits * d, dtype=torch.float32, device=q.device)
-            pml_t = torch.empty(b * hq * splits * 2, dtype=torch.float32, device=q.device)
-        else:
-            po_t, pml_t = workspace
-            if po_t.numel() < b * hq * splits * d or pml_t.numel() < b * hq * splits * 2:
-                raise ValueError("attention workspace too small")
-        po, pml = po_t.data_ptr(), pml_t.data_ptr()
-    _ext.kernels().paged_attention_decode(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                          block_tables.data_ptr(), seq_lens.data_ptr(), po, pml, b, hq, hkv, d,
-                                          bs, max_blocks, splits, split_len, float(scale), _stream())
-    return out
-
-
-def paged_attention_decode_rope(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, block_tables, seq_lens,
-                                num_heads: int, num_kv_heads: int, head_dim: int, scale: float,
-                                max_ctx: Optional[int] = None, workspace: Optional[tuple] = None):
-    """Decode attention with RoPE + KV-cache append fused in (one launch instead of two): reads the raw
-    qkv projection [B, (Hq + 2 Hkv) * D], appends each sequence's new k / v at ``slot_mapping`` and
-    attends over the whole context including it.  Same result as ``rope_cache_append`` followed by
-    ``paged_attention_decode`` (the new key is folded in last instead of inside its block).
-
-    ``qkv`` may be a :class:`gemm.SplitKPartial`: the kernel then sums the split-K slabs (f32 sums of f16 x 2^-6 slices) itself
-    (bit-identical to reducing first), which removes the reduce launch and the bf16 round trip."""
-    part = None
-    if isinstance(qkv, gemm.SplitKPartial):
-        part = qkv
-        if len(part.shape) != 2:
-            raise ValueError("qkv partial must be [B, (Hq + 2 Hkv) * D]")
-        b, width, qdtype, qdev = part.m, part.n, part.dtype, part.device
-    else:
-        b, width, qdtype, qdev = qkv.shape[0], qkv.shape[-1], qkv.dtype, qkv.device
-    if part is None and not _gpu(qkv):
-        q = ref.rope_cache_append(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, num_heads, num_kv_heads,
-                                  head_dim)
-        return ref.paged_attention_decode(q, k_cache, v_cache, block_tables, seq_lens, scale)
-    if part is None:
-        _ck(qkv, "attn.qkv")
-    _ck(k_cache, "k_cache")
-    _ck(v_cache, "v_cache")
-    _ck(positions, "positions", torch.int32)
-    _ck(slot_mapping, "slot_mapping", torch.int32)
-    _ck(block_tables, "block_tables", torch.int32)
-    _ck(seq_lens, "seq_lens", torch.int32)
-    hq, hkv, d = num_heads, num_kv_heads, head_dim
-    if width != (hq + 2 * hkv) * d:
-        raise ValueError("qkv width mismatch")
-    if cos_sin is not None:
-        _ck(cos_sin, "cos_sin", torch.float32)
-        if cos_sin.shape[1] != d:
-            raise ValueError("cos_sin width must equal head_dim")
-    bs = k_cache.shape[2]
-    max_blocks = block_tables.shape[1]
-    if max_ctx is None:
-        max_ctx = max_blocks * bs
-    if max_ctx > max_blocks * bs:
-        raise ValueError("max_ctx exceeds block table capacity")
-    splits, split_len = decode_split_plan(b, hkv, max_ctx, bs, max_blocks)
-    out = torch.empty(b, hq, d, dtype=qdtype, device=qdev)
-    po = pml = 0
-    if splits > 1:
-        if workspace is None:
-            po_t = torch.empty(b * hq * splits * d, dtype=torch.float32, device=qdev)
-            pml_t = torch.empty(b * hq * splits * 2, dtype=torch.float32, device=qdev)
-        else:
-            po_t, pml_t = workspace
-            if po_t.numel() < b * hq * splits * d or pml_t.numel() < b * hq * splits * 2:
-                raise ValueError("attention workspace too small")
-        po, pml = po_t.data_ptr(), pml_t.data_ptr()
-    _ext.kernels().paged_attention_decode_rope(
-        out.data_ptr(), 0 if part is not None else qkv.data_ptr(), positions.data_ptr(),
-        0 if cos_sin is None else cos_sin.data_ptr(),
-        slot_mapping.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(), seq_lens.data_ptr(),
-        po, pml, b, hq, hkv, d, bs, max_blocks, splits, split_len, float(scale),
-        0 if part is None else part.ws.data_ptr(), 0 if part is None else part.splits,
-        0 if part is None else part.m * part.n, _stream())
-    return out
-
-
-def prefill_attn_version(max_q_len: int, head_dim: int) -> int:
-    """The prefill attention kernel for a batch: knobs.prefill_attn, or with 0 (auto) from
-    knobs.prefill_w32_min_q query rows at head_dim 128 the persistent 32x32x16 kernel (9: 1.1x v4 at
-    64 x 512-token prompts, 1.35x at 1 x 16k; profiles/round6_attention.md) -- or its one-shot form (7)
-    while spinning comm kernels hold CUs (ops.gemm.reserve_cus_for_comm: a persistent grid sized to
-    every CU would wait for them) -- and v4 below (256 x 128-token prompts: v4 180-185 us, v9 185-193)."""
-    v = knobs.K.prefill_attn
-    if v:
-        return v
-    if head_dim != 128 or max_q_len < knobs.K.prefill_w32_min_q:
-        return 4
-    from . import gemm
-    return 7 if gemm._comm_cus else 9
-
-
-PREFILL_SPLIT = 5            # the split-context prefill kernel's version number
-PF_SPLIT_MIN_CHUNKS = 8      # KV chunks (of 32 keys) a split walks at least: its load pipeline needs a run
-PF_SPLIT_TARGET_WGS = 512    # workgroups to aim for: two per CU
-PF_SPLIT_MAX_PLAIN_WGS = 128  # the plain grid "cannot fill the device": at most half the CUs
-PF_SPLIT_MAX_Q = 64          # query rows per sequence up to which the cutover was measured (profiles/prefix_cache.md)
-
-
-def _prefill_plain_wgs(batch: int, num_kv_heads: int, max_q_len: int, group: int) -> int:
-    """Workgroups of the 16x16 prefill kernels' grid (launch_prefill: 4 waves x 2 tiles x 16/G rows)."""
-    rows_per_wg = 4 * max(1, 16 // group) * 2
-    return -(-max_q_len // rows_per_wg) * num_kv_heads * batch
-
-
-def prefill_split_plan(batch: int, num_kv_heads: int, max_q_len: int, max_ctx: int, group: int,
-                       block_size: int = 32) -> Tuple[int, int]:
-    """(nsplit, split_chunks) of the split-context prefill kernel, chosen as decode_split_plan chooses:
-    enough splits to fill the CUs (PF_SPLIT_TARGET_WGS workgroups over the kernel's own grid, which puts
-    one tile on a wave while the rows fit one workgroup), with a floor of PF_SPLIT_MIN_CHUNKS chunks per
-    split.  Split s covers the chunks [s, s + 1) x split_chunks of every sequence."""
-    rows1 = 4 * max(1, 16 // group)
-    rows_per_wg = rows1 if max_q_len <= rows1 else 2 * rows1
-    wgs = max(1, -(-max_q_len // rows_per_wg) * num_kv_heads * batch)
-    chunks = max(1, -(-max_ctx // block_size))
-    nsplit = max(1, min(-(-PF_SPLIT_TARGET_WGS // wgs), chunks // PF_SPLIT_MIN_CHUNKS))
-    split_chunks = -(-chunks // nsplit)
-    return -(-chunks // split_chunks), split_chunks
-
-
-def prefill_split_eligible(batch: int, num_kv_heads: int, max_q_len: int, max_ctx: Optional[int], group: int) -> bool:
-    """Whether a prefill call takes the split-context kernel by default: a short tail (at most
-    PF_SPLIT_MAX_Q query rows per sequence -- the range the cutover was measured in; longer chunks of a
-    chunked prompt keep the kernel they had), a plain grid that cannot fill the device (few sequences: at
-    most PF_SPLIT_MAX_PLAIN_WGS workgroups), a longest context that reaches knobs.prefill_split_min_ctx
-    (0: never) and a plan with more than one split.  The rule also bounds the partial workspace:
-    T <= 32 x PF_SPLIT_MAX_PLAIN_WGS rows."""
-    min_ctx = knobs.K.prefill_split_min_ctx
-    if not min_ctx or not max_ctx or max_ctx < min_ctx or knobs.K.prefill_attn != 0:
-        return False
-    if max_q_len > PF_SPLIT_MAX_Q:
-        return False
-    if group not in (1, 2, 4, 8, 16) or _prefill_plain_wgs(batch, num_kv_heads, max_q_len, group) > PF_SPLIT_MAX_PLAIN_WGS:
-        return False
-    return prefill_split_plan(batch, num_kv_heads, max_q_len, max_ctx, group)[0] > 1
-
-
-def _prefill_split(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, scale, max_q_len, max_ctx, out,
-                   nsplit: Optional[int], workspace: Optional[tuple]):
-    t, hq, d = q.shape
-    b = seq_lens.shape[0]
-    hkv, bs, max_blocks = k_cache.shape[1], k_cache.shape[2], block_tables.shape[1]
-    if max_ctx is None:
-        max_ctx = int(seq_lens.max().item()) if b else 0
-    if max_ctx > max_blocks * bs:
-        raise ValueError("max_ctx exceeds block table capacity")
-    chunks = max(1, -(-max_ctx // bs))
-    if nsplit is None:
-        nsplit, split_chunks = prefill_split_plan(b, hkv, int(max_q_len), max_ctx, hq // hkv, bs)
-    else:       # forced (tests, benchmarks): also more splits than chunks, the trailing ones empty
-        nsplit = int(nsplit)
-        if nsplit < 1:
-            raise ValueError("nsplit >= 1")
-        split_chunks = max(1, -(-chunks // nsplit))
-    if workspace is None:
-        po_t = torch.empty(t * hq * nsplit * d, dtype=torch.float32, device=q.device)
-        pml_t = torch.empty(t * hq * nsplit * 2, dtype=torch.float32, device=q.device)
-    else:
-        po_t, pml_t = workspace
-        if po_t.numel() < t * hq * nsplit * d or pml_t.numel() < t * hq * nsplit * 2:
-            raise ValueError("attention workspace too small")
-    _ext.kernels().paged_attention_prefill_split(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                                 block_tables.data_ptr(), cu_seqlens_q.data_ptr(), seq_lens.data_ptr(),
-                                                 po_t.data_ptr(), pml_t.data_ptr(), b, t, hq, hkv, d, bs, max_blocks,
-                                                 int(max_q_len), int(max_ctx), nsplit, split_chunks, float(scale),
-                                                 _stream())
-    return out
-
-
-def paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, scale: float,
-                            max_q_len: Optional[int] = None, version: int = 0, out: Optional[torch.Tensor] = None,
-                            max_ctx: Optional[int] = None, nsplit: Optional[int] = None,
-                            workspace: Optional[tuple] = None):
-    """``version``: prefill kernel 3, 4, 5, 7 or 9 (0: prefill_attn_version, or 5 where ``max_ctx`` -- the
-    batch's longest context, known to the host -- makes the call prefill_split_eligible); ``out`` as
-    paged_attention_decode.  Version 5 is the split-context kernel (every row of q must belong to a
-    sequence): ``nsplit`` forces its split count (None: prefill_split_plan), ``workspace`` its (o, ml)
-    partial buffers (None: allocated for the call)."""
-    if not _gpu(q):
-        return _into(out, ref.paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens,
-                                                      scale))
-    _ck(q, "attn.q")
-    _ck(k_cache, "k_cache")
-    _ck(v_cache, "v_cache")
-    _ck(block_tables, "block_tables", torch.int32)
-    _ck(cu_seqlens_q, "cu_seqlens_q", torch.int32)
-    _ck(seq_lens, "seq_lens", torch.int32)
-    t, hq, d = q.shape
-    b = seq_lens.shape[0]
-    if max_q_len is None:
-        max_q_len = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max().item()) if b else 0
-    if out is None:
-        out = torch.empty_like(q)
-    elif out.shape != q.shape or not out.is_contiguous() or out.dtype != q.dtype:
-        raise ValueError("attention out must be a contiguous tensor shaped like q")
-    hkv = k_cache.shape[1]
-    version = version or (PREFILL_SPLIT if knobs.K.prefill_attn == PREFILL_SPLIT else 0)
-    if version == PREFILL_SPLIT or (not version and prefill_split_eligible(b, hkv, int(max_q_len), max_ctx, hq // hkv)):
-        if t == 0 or b == 0:
-            return out
-        return _prefill_split(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, scale, max_q_len, max_ctx,
-                              out, nsplit, workspace)
-    _ext.kernels().paged_attention_prefill(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                           block_tables.data_ptr(), cu_seqlens_q.data_ptr(), seq_lens.data_ptr(),
-                                           b, hq, hkv, d, k_cache.shape[2], block_tables.shape[1],
-                                           int(max_q_len), float(scale), version or prefill_attn_version(int(max_q_len), d),
-                                           0, 0, 0,
-                                           _stream())
-    return out
-
-
-PF_MAX_CHUNKS = 1024    # attention.hip kPfMaxChunks: the LDS prefill kernel stages <= 32k tokens of block ids
-
-
-def prefill_rope_in_attention(max_blocks: Optional[int] = None, split_shape: Optional[tuple] = None) -> bool:
-    """Prefill q-RoPE inside the attention kernel (knobs.prefill_fused_rope; LDS kernel versions).
-    ``max_blocks``: the batch's block-table width -- beyond ``PF_MAX_CHUNKS`` (32k-token sequences)
-    the launcher falls back to the register-tiled kernel, which reads a rotated q, so the caller
-    must take ``rope_cache_append(write_q=True)`` + the plain prefill kernel instead.  The same
-    holds where the split-context kernel is chosen: ``split_shape`` = (batch, num_kv_heads, max_q_len,
-    max_ctx, group), the arguments of prefill_split_eligible."""
-    if max_blocks is not None and max_blocks > PF_MAX_CHUNKS:
-        return False
-    if split_shape is not None and prefill_split_eligible(*split_shape):
-        return False
-    return knobs.K.prefill_fused_rope and knobs.K.prefill_attn in (0, 4, 7, 9)
-
-
-def paged_attention_prefill_rope(qkv, positions, cos_sin, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens,
-                                 num_heads: int, head_dim: int, scale: float, max_q_len: Optional[int] = None,
-                                 out: Optional[torch.Tensor] = None):
-    """Prefill attention reading q straight from the qkv projection [T, (Hq + 2 Hkv) * D] and rotating it
-    in registers (K / V already appended by ``rope_cache_append(..., write_q=False)``): the rotated q
-    never round-trips through HBM.  Returns [T, Hq, D]."""
-    hkv = k_cache.shape[1]
-    t, width = qkv.shape
-    if not _gpu(qkv):
-        q = ref.rope_q(qkv, positions, cos_sin, num_heads, head_dim)
-        return _into(out, ref.paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens,
-                                                      scale))
-    _ck(qkv, "attn.qkv")
-    _ck(k_cache, "k_cache")
-    _ck(v_cache, "v_cache")
-    _ck(block_tables, "block_tables", torch.int32)
-    _ck(cu_seqlens_q, "cu_seqlens_q", torch.int32)
-    _ck(seq_lens, "seq_lens", torch.int32)
-    _ck(positions, "positions", torch.int32)
-    if width != (num_heads + 2 * hkv) * head_dim:
-        raise ValueError("qkv width mismatch")
-    if cos_sin is not None:
-        _ck(cos_sin, "cos_sin", torch.float32)
-    if not prefill_rope_in_attention(block_tables.shape[1]):
-        raise ValueError("in-kernel prefill RoPE needs an LDS prefill kernel (knobs.prefill_attn 0, 4, 7 or 9) and "
-                         f"block tables of <= {PF_MAX_CHUNKS} blocks")
-    b = seq_lens.shape[0]
-    if max_q_len is None:
-        max_q_len = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max().item()) if b else 0
-    if out is None:
-        out = torch.empty(t, num_heads, head_dim, dtype=qkv.dtype, device=qkv.device)
-    _ext.kernels().paged_attention_prefill(out.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                           block_tables.data_ptr(), cu_seqlens_q.data_ptr(), seq_lens.data_ptr(),
-                                           b, num_heads, hkv, head_dim, k_cache.shape[2], block_tables.shape[1],
-                                           int(max_q_len), float(scale), prefill_attn_version(int(max_q_len), head_dim),
-                                           positions.data_ptr(),
-                                           0 if cos_sin is None else cos_sin.data_ptr(), width, _stream())
-    return out
+# ------------------------------------------------- K4 - K7: ops/attention.py
+# (imported here, below the helpers it takes from this module)
+from .attention import (MAX_DECODE_SPLITS, PF_MAX_CHUNKS, PF_SPLIT_MAX_PLAIN_WGS, PF_SPLIT_MAX_Q,  # noqa: E402,F401
+                        PF_SPLIT_MIN_CHUNKS, PF_SPLIT_TARGET_WGS, PREFILL_SPLIT, PrefillRoute, decode_split_plan,
+                        decode_workspace, paged_attention_decode, paged_attention_decode_rope,
+                        paged_attention_prefill, paged_attention_prefill_rope, prefill_attn_version, prefill_route,
+                        prefill_split_eligible, prefill_split_plan, rope_cache_append)
 
 
 # ------------------------------------------------------------- K10

@@ -178,12 +178,12 @@ def test_mixed_prefill_decode_steps_gpu(cuda):
 
 def test_prefill_with_block_table_wider_than_lds_kernel(cuda):
     """A prefill whose block table is wider than the LDS prefill kernel stages (> 1024 blocks, i.e.
-    sequences past 32k tokens) must not take the in-kernel q-RoPE path: the launcher falls back to
+    sequences past 32k tokens) must not take the in-kernel q-RoPE path: the route falls back to
     the register-tiled kernel, which reads a rotated q.  The stage then appends with write_q=True
     and runs the plain prefill kernel -- same logits as the narrow table, within the kernels' bf16
     difference."""
     from distributed_llms_amd import knobs, ops
-    assert not ops.prefill_rope_in_attention(ops.PF_MAX_CHUNKS + 1)
+    assert not ops.prefill_route(2, 32, 8, 128, 70, None, ops.PF_MAX_CHUNKS + 1).rope_in_kernel
     _, e_gpu = _engines("tiny-llama-d128", graphs=False)
     prompts = [[1, 5, 9, 200, 37, 44, 45, 46, 47, 48], list(range(10, 80))]
     for p in prompts:

@@ -81,7 +81,7 @@ def test_prefill_split_one_tile_per_wave_exact(cuda, form):
     c = ax.prefill_case(form, 32, 8, 128, pairs)
     q, k, v, bt, cu, sl = ax._dev(c, "q", "k", "v", "bt", "cu", "sl")
     with knobs.override(prefill_attn=V5):
-        assert not ops.prefill_rope_in_attention(bt.shape[1])
+        assert not ops.prefill_route(len(pairs), 32, 8, 128, c.max_q, None, bt.shape[1]).rope_in_kernel
         ax.assert_exact(ops.paged_attention_prefill(q, k, v, bt, cu, sl, 1 / math.sqrt(c.d), max_q_len=c.max_q),
                         c.expect)
 
@@ -142,3 +142,27 @@ def test_prefill_split_chosen_by_default_from_the_knob(cuda):
         auto = ops.paged_attention_prefill(q, k, v, bt, cu, sl, scale, max_q_len=c.max_q, max_ctx=max(c.lens))
     assert torch.equal(auto, _run(c, None))
     ax.assert_exact(auto, c.expect)
+
+
+# ------------------------------------------------------------------ the route's two demotions
+def _small(d, width=None):
+    """Seeded: B = 2, query lengths (5, 33) over contexts (5, 70), hq, hkv = 4, 2; ``width``: block-table
+    columns to pad to (the padding is never read)."""
+    c = ax.prefill_case("random", 4, 2, d, ((5, 5), (70, 33)))
+    q, k, v, bt, cu, sl = ax._dev(c, "q", "k", "v", "bt", "cu", "sl")
+    if width is not None:
+        bt = torch.nn.functional.pad(bt, (0, width - bt.shape[1])).contiguous()
+    return lambda version: ops.paged_attention_prefill(q, k, v, bt, cu, sl, 1 / math.sqrt(d), max_q_len=c.max_q,
+                                                       version=version)
+
+
+@pytest.mark.gpu
+def test_w32_version_at_head_dim_64_runs_version_4(cuda):
+    run = _small(64)
+    assert torch.equal(run(9), run(4))
+
+
+@pytest.mark.gpu
+def test_lds_version_behind_a_wide_block_table_runs_version_3(cuda):
+    run = _small(128, ops.PF_MAX_CHUNKS + 1)
+    assert torch.equal(run(4), run(3))

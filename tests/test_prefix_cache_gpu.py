@@ -15,6 +15,7 @@ from distributed_llms_amd.engine.llm_engine import LLMEngine
 from distributed_llms_amd.engine.sequence import SamplingParams
 from distributed_llms_amd.models import weights as W
 from distributed_llms_amd.models.stage import ModelStage
+from distributed_llms_amd.ops import attention
 
 pytestmark = pytest.mark.gpu
 NAME = "tiny-llama-d128"
@@ -45,7 +46,8 @@ def test_tail_prefill_after_a_hit_matches_cpu_logits(cuda, attn):
             hb = build_host_batch(st, eng.bm, 32)
             logits.append(eng.runner.execute(hb).float().cpu())
         assert seq.cached_tokens == 288 and hb.num_tokens == 32 and int(hb.positions[0]) == 288
-        assert ops.prefill_rope_in_attention(hb.block_tables.shape[1]) == (attn == 0)
+        assert ops.prefill_route(1, cfg.num_heads, cfg.num_kv_heads, cfg.head_dim, hb.num_tokens, None,
+                                 hb.block_tables.shape[1]).rope_in_kernel == (attn == 0)
     torch.testing.assert_close(logits[1], logits[0], atol=6e-2, rtol=5e-2)
 
 
@@ -65,7 +67,7 @@ def _count_attention_paths(monkeypatch):
     """Counters of the calls that reach the split kernel, the in-kernel-RoPE prefill and the
     rotated-q append, as the stage makes them."""
     n = {"split": 0, "rope_attn": 0, "write_q": 0}
-    split, rope_attn, append = ops._prefill_split, ops.paged_attention_prefill_rope, ops.rope_cache_append
+    split, rope_attn, append = attention._prefill_split, ops.paged_attention_prefill_rope, ops.rope_cache_append
 
     def count(key, fn, when=lambda a, k: True):
         def wrapped(*a, **k):
@@ -73,7 +75,7 @@ def _count_attention_paths(monkeypatch):
             return fn(*a, **k)
         return wrapped
 
-    monkeypatch.setattr(ops, "_prefill_split", count("split", split))
+    monkeypatch.setattr(attention, "_prefill_split", count("split", split))
     monkeypatch.setattr(ops, "paged_attention_prefill_rope", count("rope_attn", rope_attn))
     monkeypatch.setattr(ops, "rope_cache_append", count("write_q", append, lambda a, k: k.get("write_q", True)))
     return n

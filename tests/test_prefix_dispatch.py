@@ -38,17 +38,19 @@ def test_split_kernel_eligibility():
 
 
 def test_rope_in_attention_off_where_the_split_kernel_is_chosen():
-    shape = (1, 8, 20, 8192, 4)                             # batch, kv heads, max_q_len, max_ctx, group
+    def rope(max_blocks, batch=1, max_q_len=20, max_ctx=None):      # Llama-3-8B heads
+        return ops.prefill_route(batch, 32, 8, 128, max_q_len, max_ctx, max_blocks).rope_in_kernel
+
     with knobs.override(prefill_attn=0, prefill_fused_rope=True, prefill_split_min_ctx=4096):
-        assert ops.prefill_rope_in_attention(256)
-        assert not ops.prefill_rope_in_attention(256, shape)
-        assert ops.prefill_rope_in_attention(256, (256, 8, 128, 128, 4))     # the flagship prefill: untouched
-        assert ops.prefill_rope_in_attention(256, (1, 8, 20, 4000, 4))
-        assert ops.prefill_rope_in_attention(256, (1, 8, 512, 8192, 4))      # a 512-row chunk over 8k: untouched
+        assert rope(256)
+        assert not rope(256, 1, 20, 8192)
+        assert rope(256, 256, 128, 128)             # the flagship prefill: untouched
+        assert rope(256, 1, 20, 4000)
+        assert rope(256, 1, 512, 8192)              # a 512-row chunk over 8k: untouched
     with knobs.override(prefill_attn=0, prefill_fused_rope=True, prefill_split_min_ctx=0):
-        assert ops.prefill_rope_in_attention(256, shape)
+        assert rope(256, 1, 20, 8192)
     with knobs.override(prefill_attn=ops.PREFILL_SPLIT, prefill_fused_rope=True):
-        assert not ops.prefill_rope_in_attention(16)        # forced: every prefill call reads a rotated q
+        assert not rope(16)                         # forced: every prefill call reads a rotated q
 
 
 def test_split_plan_fills_the_cus_with_a_floor():

@@ -266,16 +266,19 @@ def test_lm_head_leaves_gemm_pp_while_comm_cus_are_reserved():
     assert calls == ["pp", "wide"]
 
 
-def test_prefill_rope_in_attention_gated_on_block_table_width():
+def test_rope_in_kernel_gated_on_block_table_width():
     """Advisor round 5: block tables wider than the LDS prefill kernel stages (sequences past 32k
     tokens) must take the write_q=True append + plain prefill kernel, not the in-kernel q-RoPE."""
     from distributed_llms_amd import knobs, ops
+    def rope(max_blocks):                            # Llama-3-8B heads, one 20-token prompt
+        return ops.prefill_route(1, 32, 8, 128, 20, None, max_blocks).rope_in_kernel
+
     with knobs.override(prefill_attn=4, prefill_fused_rope=True):
-        assert ops.prefill_rope_in_attention()
-        assert ops.prefill_rope_in_attention(ops.PF_MAX_CHUNKS)
-        assert not ops.prefill_rope_in_attention(ops.PF_MAX_CHUNKS + 1)
+        assert rope(16)
+        assert rope(ops.PF_MAX_CHUNKS)
+        assert not rope(ops.PF_MAX_CHUNKS + 1)
     with knobs.override(prefill_attn=3, prefill_fused_rope=True):
-        assert not ops.prefill_rope_in_attention(16)
+        assert not rope(16)
 
 
 def test_prefill_attention_auto_version():
@@ -290,7 +293,7 @@ def test_prefill_attention_auto_version():
         assert ops.prefill_attn_version(512, 128) == 9
         assert ops.prefill_attn_version(16384, 128) == 9
         assert ops.prefill_attn_version(4096, 64) == 4
-        assert ops.prefill_rope_in_attention(64)
+        assert ops.prefill_route(1, 32, 8, 128, 20, None, 64).rope_in_kernel
         gemm.reserve_cus_for_comm(16)
         try:
             assert ops.prefill_attn_version(4096, 128) == 7

@@ -278,6 +278,12 @@ class EngineConfig:
     request_timeout: float = 600.0
     seed: int = 0
     shard_dir: Optional[str] = None    # checkpoint dir (shards/); None -> synthetic init
+    # LoRA adapters served next to the base model (models/lora.py): name -> a local PEFT directory or
+    # "synthetic:<rank>:<seed>[:<module>+...]".  A request picks one with SamplingParams.adapter; the
+    # set is fixed for the engine's life and workers need the paths too.  Not with quant="fp8",
+    # GPT-2, tensor parallelism (tp > 1) or sub-layer pipeline cuts
+    lora_modules: Dict[str, str] = field(default_factory=dict)
+    max_lora_rank: int = 64
     log_level: str = "INFO"
 
     def validate(self) -> None:
@@ -306,12 +312,19 @@ class EngineConfig:
         cfg = get_model_config(self.model if self.shard_dir is None else self.shard_dir)
         if self.num_workers > cfg.num_layers:
             raise ValueError(f"{self.num_workers} stages > {cfg.num_layers} layers")
+        if self.lora_modules:
+            if not isinstance(self.lora_modules, dict):
+                raise ValueError("lora_modules must map adapter names to sources")
+            from .models.lora import check_engine
+            check_engine(self, cfg)
 
     def check_tensor_parallel(self, tp: int) -> None:
         """What a tensor-parallel layout (``tp`` ranks per stage) cannot run; every rank calls it with the
         same arguments before it builds anything, so all of them refuse together."""
         if tp > 1 and self.enable_prefix_caching:
             raise ValueError("prefix caching is not supported with tensor parallelism (tp > 1)")
+        if tp > 1 and self.lora_modules:
+            raise ValueError("LoRA adapters are not supported with tensor parallelism (tp > 1)")
 
     def model_config(self) -> ModelConfig:
         return get_model_config(self.shard_dir or self.model)

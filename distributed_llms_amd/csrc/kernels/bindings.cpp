@@ -24,6 +24,9 @@ PYBIND11_MODULE(_C_kernels, m) {
   m.def("logit_state_update", &dllm::logit_state_update);
   m.def("logit_state_count", &dllm::logit_state_count);
   m.attr("PROC_WORDS") = dllm::kProcWords;
+  m.def("lora_ksplit", &dllm::lora_ksplit);
+  m.def("lora_shrink", &dllm::lora_shrink);
+  m.def("lora_expand", &dllm::lora_expand);
   m.def("add_inplace", &dllm::add_inplace);
   m.def("moe_route", &dllm::moe_route);
   m.def("moe_grouped_gemm", &dllm::moe_grouped_gemm);

@@ -45,6 +45,16 @@ void logit_state_update(uintptr_t state, int pitch, int state_rows, int vocab, u
 void logit_state_count(uintptr_t state, int pitch, int state_rows, int vocab, uintptr_t ids, uintptr_t procs, int rows,
                        uintptr_t stream);
 
+// lora.hip: per-row adapters after a projection.  tile_slot [nt] / tile_rows [nt * 16] i32: the step's row plan
+// (-1: unused tile / padding); A [slots, R, K] bf16 (R = slices x rp), B [slots, N, rp] bf16, scale [slots] f32;
+// ws: f32 [lora_ksplit(K), nt * 16, R]; off1 / off2: first column of slice 1 / 2 (N when there is none)
+int lora_ksplit(int K);
+void lora_shrink(uintptr_t ws, long ws_floats, uintptr_t x, uintptr_t A, uintptr_t tile_slot, uintptr_t tile_rows,
+                 int T, int K, int R, int nslots, int nt, uintptr_t stream);
+void lora_expand(uintptr_t y, long ldy, uintptr_t ws, long ws_floats, uintptr_t B, uintptr_t scale,
+                 uintptr_t tile_slot, uintptr_t tile_rows, int T, int N, int K, int R, int rp, int off1, int off2,
+                 int nslots, int nt, uintptr_t stream);
+
 void splitk_add_rms_norm(uintptr_t y, uintptr_t residual, uintptr_t ws, int S, int M, int N, uintptr_t w, float eps,
                          uintptr_t stream);
 void splitk_reduce(uintptr_t out, uintptr_t ws, uintptr_t bias, int S, int M, int N, uintptr_t stream);

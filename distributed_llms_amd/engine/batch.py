@@ -60,6 +60,10 @@ class HostBatch:
     bias_ids: Optional[np.ndarray] = None
     bias_vals: Optional[np.ndarray] = None
     state_rows: int = 0
+    # [B] int32: each row's LoRA adapter slot (-1: the base model); None when no row of the step has an
+    # adapter -- the packed array is then what it was without the field and no LoRA kernel runs.
+    # Packed after the processors section with header word 13 set
+    lora: Optional[np.ndarray] = None
 
     @property
     def num_tokens(self) -> int:
@@ -82,8 +86,10 @@ class HostBatch:
         has_seeds = 1 if self.sample_seeds is not None else 0
         has_lp = 1 if self.logprobs is not None else 0
         has_pr = 1 if self.procs is not None else 0
+        has_lo = 1 if self.lora is not None else 0
         hdr = np.array([1 if self.is_prefill else 0, t, b, mb, self.max_q_len, self.max_ctx, self.slot,
-                        self.step_id, has_s, self.num_decode, has_seeds, has_lp, has_pr] + [0] * 3, dtype=np.int32)
+                        self.step_id, has_s, self.num_decode, has_seeds, has_lp, has_pr, has_lo] + [0] * 2,
+                       dtype=np.int32)
         parts = [hdr, self.ids, self.positions, self.slots, self.seq_lens, self.cu_seqlens,
                  self.block_tables.reshape(-1), self.logits_idx]
         if has_s:
@@ -95,6 +101,8 @@ class HostBatch:
         if has_pr:
             parts += [np.array([self.state_rows], dtype=np.int32), self.procs.reshape(-1), self.bias_cu,
                       self.bias_ids, self.bias_vals]
+        if has_lo:
+            parts.append(self.lora)
         return np.concatenate([p.astype(np.int32, copy=False).reshape(-1) for p in parts])
 
     def sampling_args(self) -> dict:
@@ -133,6 +141,8 @@ class HostBatch:
             hb.procs, hb.bias_cu = take(PROC_WORDS * b).reshape(b, PROC_WORDS), take(b + 1)
             nb = int(hb.bias_cu[-1])
             hb.bias_ids, hb.bias_vals = take(nb), take(nb)
+        if int(hdr[13]):
+            hb.lora = take(b)
         return hb
 
 
@@ -170,6 +180,22 @@ def attach_procs(hb: HostBatch, seqs, state_rows: int, prefill: bool) -> None:
     hb.raw = None            # a natively packed batch: pack() concatenates again, section included
 
 
+def attach_lora(hb: HostBatch, seqs) -> None:
+    """Give ``hb`` its lora section when a row of it has an adapter.  ``seqs``: the batch's sequences
+    in row order (as attach_procs takes them)."""
+    if not any(s.lora_slot >= 0 for s in seqs):
+        return
+    hb.lora = np.fromiter((s.lora_slot for s in seqs), dtype=np.int32, count=len(seqs))
+    hb.raw = None            # a natively packed batch: pack() concatenates again, section included
+
+
+def token_lora_slots(hb: HostBatch) -> np.ndarray:
+    """The per-token adapter slots of a batch with a lora section (a row's tokens share its slot)."""
+    if not hb.is_prefill:
+        return hb.lora
+    return np.repeat(hb.lora, np.diff(hb.cu_seqlens))
+
+
 def next_pow2(x: int, lo: int = 1) -> int:
     p = lo
     while p < x:
@@ -183,17 +209,23 @@ def build_host_batch(step: Step, bm, block_size: int, max_blocks: Optional[int] 
     block-table width is the scheduler's ``max_blocks``); only the step id is stamped here.  A
     mixed step is the decode rows' packed batch followed by its prefill chunk's (merge_mixed)."""
     state_rows = getattr(step, "state_rows", 0)
+    lora = getattr(step, "lora", False)
     if getattr(step, "mixed", False):
         dec = HostBatch.unpack(step.packed)
         if state_rows:
             attach_procs(dec, step.decode_seqs, state_rows, False)
-        pre = build_host_batch(Step(True, step.seqs, step.slot, state_rows=state_rows), bm, block_size, None, step_id)
+        if lora:
+            attach_lora(dec, step.decode_seqs)
+        pre = build_host_batch(Step(True, step.seqs, step.slot, state_rows=state_rows, lora=lora), bm, block_size,
+                               None, step_id)
         return merge_mixed(dec, pre, step.slot, step_id)
     if step.packed is not None:
         step.packed[7] = step_id
         hb = HostBatch.unpack(step.packed)
         if state_rows:
             attach_procs(hb, step.seqs, state_rows, False)
+        if lora:
+            attach_lora(hb, step.seqs)
         return hb
     seqs = step.seqs
     b = len(seqs)
@@ -248,6 +280,8 @@ def build_host_batch(step: Step, bm, block_size: int, max_blocks: Optional[int] 
                    max_ctx, step.slot, step_id, sampling, sample_seeds=seeds, logprobs=lps)
     if state_rows:
         attach_procs(hb, seqs, state_rows, step.is_prefill)
+    if lora:
+        attach_lora(hb, seqs)
     return hb
 
 
@@ -297,6 +331,10 @@ def merge_mixed(dec: HostBatch, pre: HostBatch, slot: int, step_id: int) -> Host
         hb.bias_ids = pre.bias_ids if pre.procs is not None else np.zeros(0, np.int32)
         hb.bias_vals = pre.bias_vals if pre.procs is not None else np.zeros(0, np.int32)
         hb.state_rows = max(dec.state_rows, pre.state_rows)
+    if dec.lora is not None or pre.lora is not None:
+        hb.lora = np.concatenate([dec.lora if dec.lora is not None else np.full(nd, -1, np.int32),
+                                  pre.lora if pre.lora is not None
+                                  else np.full(pre.num_seqs, -1, np.int32)]).astype(np.int32)
     return hb
 
 
@@ -344,4 +382,7 @@ def to_device_meta(hb: HostBatch, device, pad_ctx_to: Optional[int] = None) -> (
         meta.max_ctx_d = int(hb.seq_lens[:nd].max())
         meta.max_q_len_p = int((hb.cu_seqlens[nd + 1:] - hb.cu_seqlens[nd:-1]).max())
         meta.max_ctx_p = int(hb.seq_lens[nd:].max())
+    if hb.lora is not None:
+        from ..ops import lora
+        meta.lora = lora.make_plan(token_lora_slots(hb), dev)
     return ids, meta

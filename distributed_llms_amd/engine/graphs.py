@@ -5,16 +5,23 @@ each on the host, so the step is captured once per (batch bucket, context bucket
 replayed.  Inputs are copied into persistent device buffers; padded rows of a bucket
 write their K/V into the reserved scratch block 0 (slot 0) and attend to one token,
 so they never touch a live sequence.
+
+Steps with LoRA adapter rows replay a variant of their own, keyed (batch bucket, context bucket,
+True): its forward runs the adapter kernels over a static row plan sized for the bucket's largest
+tile count, filled per step with one more H2D copy (padded rows: slot -1).  Steps without adapter
+rows replay the (..., False) graphs and copy nothing new.
 """
 from __future__ import annotations
 
 import threading
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from .. import ops
 from ..models.stage import BatchMeta, ModelStage
+from ..ops import lora as lora_ops
 from .batch import HostBatch, next_pow2
 
 SCRATCH_SEQ_ID = -1      # owns block 0 in the BlockManager
@@ -49,7 +56,13 @@ class DecodeGraphRunner:
         self.ws = ops.decode_workspace(mb, cfg.num_heads, cfg.head_dim, dev)
         self.pinned = torch.empty(4 * mb + mb * max_blocks, dtype=torch.int32).pin_memory()
         self.pinned_np = self.pinned.numpy()
-        self.graphs: Dict[Tuple[int, int], Tuple[torch.cuda.CUDAGraph, torch.Tensor]] = {}
+        self.graphs: Dict[Tuple[int, int, bool], Tuple[torch.cuda.CUDAGraph, torch.Tensor]] = {}
+        self.num_replays: Dict[Tuple[int, int, bool], int] = {}
+        # LoRA variant: [token_slot x max_batch | tile_slot x max_nt | tile_rows x 16 max_nt], allocated
+        # with the first adapter step
+        self.lora_slots = len(stage.lora.names) if stage.lora is not None else 0
+        self.lora_nt = lora_ops.max_tiles(mb, self.lora_slots)
+        self.lora_dev = self.lora_pinned = None
         self.pool = None
         self.copy_done: Optional[torch.cuda.Event] = None
         self.capture_stream: Optional[torch.cuda.Stream] = None
@@ -62,20 +75,34 @@ class DecodeGraphRunner:
     def can_run(self, b: int, max_ctx: int) -> bool:
         return b <= self.max_batch and max_ctx <= self.max_blocks * self.block_size
 
-    def _meta(self, bb: int, cb: int) -> BatchMeta:
+    def _lora_buffers(self):
+        if self.lora_dev is None:
+            n = self.max_batch + (1 + lora_ops.TILE) * self.lora_nt
+            self.lora_dev = torch.full((n,), -1, dtype=torch.int32, device=self.dev)
+            self.lora_pinned = torch.full((n,), -1, dtype=torch.int32).pin_memory()
+        return self.lora_dev
+
+    def _lora_plan(self, bb: int) -> lora_ops.LoraPlan:
+        """The bucket's static plan: views of the LoRA buffer, as many tiles as ``bb`` rows can need."""
+        buf, mb, nt = self._lora_buffers(), self.max_batch, lora_ops.max_tiles(bb, self.lora_slots)
+        t0 = mb + self.lora_nt
+        return lora_ops.LoraPlan(buf[:bb], buf[mb:mb + nt], buf[t0:t0 + nt * lora_ops.TILE], nt)
+
+    def _meta(self, bb: int, cb: int, lora: bool = False) -> BatchMeta:
         return BatchMeta(is_prefill=False, positions=self.positions[:bb], slot_mapping=self.slots[:bb],
                          block_tables=self.block_tables[:bb], seq_lens=self.seq_lens[:bb], max_q_len=1,
-                         max_ctx=cb, num_seqs=bb, num_tokens=bb, attn_workspace=self.ws)
+                         max_ctx=cb, num_seqs=bb, num_tokens=bb, attn_workspace=self.ws,
+                         lora=self._lora_plan(bb) if lora else None)
 
     def _inp(self, bb: int) -> torch.Tensor:
         return self.ids[:bb] if self.stage.is_first else self.hidden[:bb]
 
-    def capture(self, bb: int, cb: int):
+    def capture(self, bb: int, cb: int, lora: bool = False):
         with _CAPTURE_LOCK:
-            return self._capture(bb, cb)
+            return self._capture(bb, cb, lora)
 
-    def _capture(self, bb: int, cb: int):
-        meta = self._meta(bb, cb)
+    def _capture(self, bb: int, cb: int, lora: bool = False):
+        meta = self._meta(bb, cb, lora)
         # warm up outside capture (allocator, lazy module init)
         if self.capture_stream is None:
             self.capture_stream = torch.cuda.Stream(self.dev)
@@ -92,7 +119,7 @@ class DecodeGraphRunner:
         # thread_local mode: RCCL/gloo threads of this process may keep calling HIP meanwhile
         with torch.cuda.graph(g, pool=self.pool, stream=s, capture_error_mode="thread_local"):
             out = self.stage.forward(self._inp(bb), meta)
-        self.graphs[(bb, cb)] = (g, out)
+        self.graphs[(bb, cb, lora)] = (g, out)
         return g, out
 
     def load_inputs(self, hb: HostBatch, bb: int, hidden: Optional[torch.Tensor] = None):
@@ -120,6 +147,18 @@ class DecodeGraphRunner:
         bt[b:] = 0
         cnt = 4 * mb + n * w
         self.dev_in[:cnt].copy_(self.pinned[:cnt], non_blocking=True)
+        if hb.lora is not None:
+            # the step's row plan into the bucket's static one (padded rows: no adapter)
+            dev, lp = self._lora_buffers(), self.lora_pinned.numpy()
+            slots = np.full(n, -1, dtype=np.int32)
+            slots[:b] = hb.lora
+            nt = lora_ops.max_tiles(n, self.lora_slots)
+            tile_slot, tile_rows = lora_ops.row_plan(slots, nt)
+            t0 = mb + self.lora_nt
+            lp[:n] = slots
+            lp[mb:mb + nt] = tile_slot
+            lp[t0:t0 + nt * lora_ops.TILE] = tile_rows
+            dev.copy_(self.lora_pinned, non_blocking=True)
         if self.copy_done is None:
             self.copy_done = torch.cuda.Event()
         self.copy_done.record()
@@ -137,9 +176,11 @@ class DecodeGraphRunner:
         self.load_inputs(hb, bb, hidden)
         if ids_dev is not None:
             self.ids[:b].copy_(ids_dev, non_blocking=True)
-        entry = self.graphs.get((bb, cb))
+        key = (bb, cb, hb.lora is not None)
+        entry = self.graphs.get(key)
         if entry is None:
-            entry = self.capture(bb, cb)
+            entry = self.capture(*key)
+        self.num_replays[key] = self.num_replays.get(key, 0) + 1
         g, out = entry
         g.replay()
         return out[:b]

@@ -26,7 +26,9 @@ from .runner import StageRunner
 from .sampler import ids_message_len, max_ids_message_len, sample_step, unpack_ids_message
 from .scheduler import Scheduler, Step
 from .logit_state import LogitState
-from .sequence import SamplingParams, Sequence, request_seed, validate_logprobs, validate_processors
+from ..models.lora import adapter_slots
+from .sequence import (SamplingParams, Sequence, request_seed, resolve_adapter, validate_logprobs,
+                       validate_processors)
 
 log = logging.getLogger("dllm.engine")
 
@@ -55,7 +57,7 @@ def build_stage(ecfg: EngineConfig, layer_start: int = 0, layer_end: Optional[in
         stage.load_hf_state(shard_state)
     else:
         stage.init_synthetic(ecfg.seed)
-    return stage.quantize(ecfg.quant)
+    return stage.quantize(ecfg.quant).load_lora(ecfg)
 
 
 class LLMEngine:
@@ -66,6 +68,9 @@ class LLMEngine:
         if not (self.stage.is_first and self.stage.is_last):
             raise ValueError("LLMEngine needs a stage owning every layer")
         self.mcfg = self.stage.cfg
+        if ecfg.lora_modules and self.stage.lora is None:
+            self.stage.load_lora(ecfg)
+        self.adapter_slots = adapter_slots(ecfg)
         gpu = self.stage.device.type == "cuda"
         # tensor parallel leader: every step's metadata goes to the group before it runs, and the
         # followers join its collectives (parallel/tensor_parallel.py); synchronous steps, one
@@ -115,7 +120,9 @@ class LLMEngine:
         if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
             # the processors rewrite whole logit rows; the tensor-parallel lanes hold vocabulary shards
             raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
-        seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id)
+        slot = resolve_adapter(params.adapter, self.adapter_slots)
+        seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id,
+                       lora_slot=slot)
         seq.seed = request_seed(seq.params, self._seed_rng)
         self.scheduler.add(seq)
         return seq

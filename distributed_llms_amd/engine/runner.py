@@ -137,5 +137,5 @@ class StageRunner:
             for b in (batch_sizes or gr.batch_sizes):
                 for c in ctx_buckets:
                     bb, cb = gr.bucket(b, c)
-                    if (bb, cb) not in gr.graphs:
+                    if (bb, cb, False) not in gr.graphs:
                         gr.capture(bb, cb)

@@ -33,15 +33,18 @@ class Step:
     the slot's decode rows (``rows`` / ``packed``, one token each, first in the batch) and a bounded
     prefill chunk over ``seqs``."""
 
-    __slots__ = ("is_prefill", "_seqs", "slot", "rows", "packed", "keep", "_live", "mixed", "state_rows")
+    __slots__ = ("is_prefill", "_seqs", "slot", "rows", "packed", "keep", "_live", "mixed", "state_rows", "lora")
 
     def __init__(self, is_prefill: bool, seqs: Optional[List[Sequence]] = None, slot: int = 0,
                  rows: Optional[np.ndarray] = None, packed: Optional[np.ndarray] = None,
                  keep: Optional[np.ndarray] = None, live: Optional[Dict[int, Sequence]] = None,
-                 mixed: bool = False, state_rows: int = 0):
+                 mixed: bool = False, state_rows: int = 0, lora: bool = False):
         # state_rows: the LogitState row count while any request holds a state row, else 0 (the
         # step's batch then gets no processors section and nobody looks at its sequences for one)
         self.state_rows = state_rows
+        # lora: whether any request with a LoRA adapter is in the engine (else the step's batch gets no
+        # lora section and nobody looks at its sequences for one)
+        self.lora = lora
         self.is_prefill = is_prefill
         self._seqs = seqs
         self.slot = slot
@@ -145,9 +148,12 @@ class Scheduler:
         self._pending: Dict[int, set] = {}
         self._pending_of: Dict[int, List[int]] = {}
         self.num_deferrals = 0
+        self._lora_seqs = 0        # requests with a LoRA adapter added and not yet popped as finished
 
     # ------------------------------------------------------------ requests
     def add(self, seq: Sequence) -> None:
+        if seq.lora_slot >= 0:
+            self._lora_seqs += 1
         if len(seq.prompt) + 1 > self.max_seq_len:
             seq.finish("too_long")
             self.finished.append(seq)
@@ -234,7 +240,7 @@ class Scheduler:
 
     def _register_prompt(self, seq: Sequence) -> None:
         n = min(seq.num_cached, len(seq.prompt))
-        if n >= self.bm.block_size:
+        if n >= self.bm.block_size and seq.lora_slot < 0:
             self.bm.register_prefix(seq.seq_id, self._prompt(seq), n)
 
     def prefix_stats(self) -> Dict[str, int]:
@@ -245,7 +251,7 @@ class Scheduler:
     def _step(self, *args, **kw) -> Step:
         """A step about to be handed out (every one of them comes back through complete())."""
         self._issued += 1
-        return Step(*args, state_rows=self.state_rows if self._rows_held else 0, **kw)
+        return Step(*args, state_rows=self.state_rows if self._rows_held else 0, lora=self._lora_seqs > 0, **kw)
 
     def has_work(self) -> bool:
         return bool(self.waiting) or self.native.num_running_total() > 0
@@ -284,7 +290,8 @@ class Scheduler:
         deferred: List[Sequence] = []       # passed over for a pending key; they keep their queue position
         while self.waiting and n_running + len(admitted) < target:
             seq = self.waiting[0]
-            if self.prefix and seq.num_cached == 0 and not self.bm.has_sequence(seq.seq_id):
+            # a sequence with a LoRA adapter neither queries nor registers blocks: its K/V depend on the adapter
+            if self.prefix and seq.lora_slot < 0 and seq.num_cached == 0 and not self.bm.has_sequence(seq.seq_id):
                 toks = self._tokens(seq)
                 if self._gains_by_waiting(toks):
                     deferred.append(self.waiting.popleft())
@@ -316,7 +323,7 @@ class Scheduler:
             seq.slot = slot
             admitted.append(seq)
             tokens += n
-            if self.prefix:
+            if self.prefix and seq.lora_slot < 0:
                 seq.cached_tokens += seq.prefix_hit
                 seq.prefix_hit = 0
                 seq.prefix_queried = False      # a re-admission after preemption is a new query
@@ -515,4 +522,6 @@ class Scheduler:
 
     def pop_finished(self) -> List[Sequence]:
         f, self.finished = self.finished, []
+        if self._lora_seqs:
+            self._lora_seqs -= sum(1 for s in f if s.lora_slot >= 0)
         return f

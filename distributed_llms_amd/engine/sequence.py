@@ -40,6 +40,8 @@ class SamplingParams:
     frequency_penalty: float = 0.0      # [-2, 2]; times the output count
     logit_bias: Optional[Dict[int, float]] = None    # <= MAX_LOGIT_BIAS entries, values in [-100, 100]
     min_tokens: int = 0                 # EOS cannot be drawn before this many output tokens
+    # the LoRA adapter the request runs with (a name of EngineConfig.lora_modules); None: the base model
+    adapter: Optional[str] = None
 
     @property
     def has_processors(self) -> bool:
@@ -128,6 +130,16 @@ def validate_processors(params, vocab_size: int) -> bool:
     return rep != 1.0 or pres != 0.0 or freq != 0.0 or bool(bias) or mt > 0
 
 
+def resolve_adapter(adapter, slots: Dict[str, int]) -> int:
+    """The slot of a request's ``adapter`` among the engine's adapters (``slots``: name -> slot,
+    models/lora.py adapter_slots), -1 for None; an unknown name raises ValueError."""
+    if adapter is None:
+        return -1
+    if not isinstance(adapter, str) or adapter not in slots:
+        raise ValueError(f"unknown adapter {adapter!r} (configured: {sorted(slots)})")
+    return slots[adapter]
+
+
 _ids = itertools.count(1)
 
 SEED_MASK = (1 << 64) - 1
@@ -184,6 +196,8 @@ class Sequence:
     # (a sequence that found nothing and could not be admitted is looked up again on every pass), and
     # the prompt ids as the int32 array the block manager takes (made once by the scheduler)
     prefix_queried: bool = False
+    # the slot of params.adapter among the engine's adapters (resolve_adapter), -1: the base model
+    lora_slot: int = -1
     prompt_i32: Optional[Any] = field(default=None, repr=False, compare=False)
 
     def __post_init__(self):

@@ -33,6 +33,11 @@ dependency; every request thread only submits to the master's request futures):
                                prompt once and "usage.prompt_tokens_details.cached_tokens" the prompt tokens
                                found in the prefix cache (EngineConfig.enable_prefix_caching); /generate with
                                k > 1: {"results": [the k replies]}.  Anything else: 400
+  "adapter": name              (either POST, also with "stream" and "n") run the request with that LoRA adapter
+                               of EngineConfig.lora_modules; a "model" equal to a configured adapter name
+                               selects it too (any other "model" value is ignored).  An unknown "adapter":
+                               400.  The reply's "model" is the adapter's name when one ran; GET /status
+                               lists the configured names under "adapters"
   "stream": true               (either POST, one prompt) server-sent events: one ``data: {...}`` event
                                per pipeline step that produced tokens (TOKENS messages from stage 0),
                                then ``data: [DONE]`` (not together with "logprobs": 400)
@@ -58,8 +63,16 @@ _PARAM_KEYS = ("temperature", "top_k", "top_p", "ignore_eos", "seed", "logprobs"
 
 
 def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_new_tokens",
-              vocab_size: int = 1 << 31) -> Dict[str, Any]:
+              vocab_size: int = 1 << 31, adapters=()) -> Dict[str, Any]:
+    """``adapters``: the configured LoRA adapter names."""
     p = {k: body[k] for k in _PARAM_KEYS if k in body}
+    adapter = body.get("adapter")
+    if adapter is None and isinstance(body.get("model"), str) and body["model"] in adapters:
+        adapter = body["model"]
+    if adapter is not None:
+        if not isinstance(adapter, str) or adapter not in adapters:
+            raise ValueError(f"unknown adapter {adapter!r} (configured: {sorted(adapters)})")
+        p["adapter"] = adapter
     p["max_new_tokens"] = int(body.get(max_key, body.get("max_new_tokens", default_max)))
     if p["max_new_tokens"] < 1:
         raise ValueError("max tokens must be >= 1")
@@ -187,7 +200,9 @@ class _Handler(BaseHTTPRequestHandler):
         if not ids:
             raise ValueError("empty prompt")
         params = _sampling(body, default_max=16 if completions else 64,
-                           max_key="max_tokens" if completions else "max_new_tokens", vocab_size=self._vocab())
+                           max_key="max_tokens" if completions else "max_new_tokens", vocab_size=self._vocab(),
+                           adapters=self._adapters())
+        model = params.get("adapter") or self.master.model_spec
         gen = self.master.stream(ids, timeout=self.timeout_s, **params)
         first = next(gen, None)                       # errors before the first byte -> HTTP status
         self.send_response(200)
@@ -199,7 +214,7 @@ class _Handler(BaseHTTPRequestHandler):
 
         def event(chunk):
             if completions:
-                obj = {"object": "text_completion", "model": self.master.model_spec,
+                obj = {"object": "text_completion", "model": model,
                        "choices": [{"index": 0, "text": tok.decode(chunk), "tokens": chunk, "finish_reason": None}]}
             else:
                 obj = {"tokens": chunk, "text": tok.decode(chunk)}
@@ -220,6 +235,10 @@ class _Handler(BaseHTTPRequestHandler):
     def _vocab(self) -> int:
         cfg = getattr(self.master, "model_config", None)
         return int(cfg.vocab_size) if cfg is not None else 1 << 31
+
+    def _adapters(self):
+        cfg = getattr(self.master, "config", None)
+        return tuple(getattr(cfg, "lora_modules", None) or ())
 
     def _ids(self, prompt) -> List[int]:
         if isinstance(prompt, str):
@@ -250,8 +269,11 @@ class _Handler(BaseHTTPRequestHandler):
     def _generate(self, body: Dict[str, Any]) -> Dict[str, Any]:
         ids = body["prompt_ids"] if "prompt_ids" in body else self._ids(body.get("prompt", ""))
         n = _num_completions(body)
-        res = self._run([self._ids(ids)], _sampling(body, vocab_size=self._vocab()), n)
+        params = _sampling(body, vocab_size=self._vocab(), adapters=self._adapters())
+        res = self._run([self._ids(ids)], params, n)
         for r in res:
+            if params.get("adapter"):
+                r["model"] = params["adapter"]
             if "logprobs" in r:
                 r["logprobs"] = _generate_logprobs(r["logprobs"])
         return res[0] if n == 1 else {"results": res}
@@ -263,7 +285,9 @@ class _Handler(BaseHTTPRequestHandler):
         else:
             prompts = [self._ids(prompt)]
         n = _num_completions(body)
-        res = self._run(prompts, _sampling(body, default_max=16, max_key="max_tokens", vocab_size=self._vocab()), n)
+        params = _sampling(body, default_max=16, max_key="max_tokens", vocab_size=self._vocab(),
+                           adapters=self._adapters())
+        res = self._run(prompts, params, n)
         choices = [{"index": i, "text": r["text"], "tokens": r["tokens"],
                     "finish_reason": "length" if r.get("finish_reason") in ("length", "max_seq_len") else "stop"}
                    for i, r in enumerate(res)]
@@ -273,7 +297,7 @@ class _Handler(BaseHTTPRequestHandler):
         ptok = sum(len(p) for p in prompts)
         ctok = sum(len(r["tokens"]) for r in res)
         return {"id": res[0].get("task_id"), "object": "text_completion", "created": int(time.time()),
-                "model": self.master.model_spec, "choices": choices,
+                "model": params.get("adapter") or self.master.model_spec, "choices": choices,
                 "usage": {"prompt_tokens": ptok, "completion_tokens": ctok, "total_tokens": ptok + ctok,
                           "prompt_tokens_details": {"cached_tokens": sum(int(r.get("cached_tokens") or 0)
                                                                          for r in res)}}}

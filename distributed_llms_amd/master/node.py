@@ -32,7 +32,8 @@ import time
 from typing import Any, Dict, List, Optional, Sequence
 
 from ..config import EngineConfig, ModelConfig, get_model_config
-from ..engine.sequence import validate_logprobs, validate_processors
+from ..engine.sequence import resolve_adapter, validate_logprobs, validate_processors
+from ..models.lora import adapter_slots
 from ..network.protocol import MessageProtocol, pack_ids, unpack_ids, unpack_result
 from ..utils.metrics import RequestMetrics
 from ..utils.tokenizer import get_tokenizer
@@ -536,6 +537,7 @@ class MasterNode:
         if params.get("logprobs") is not None and params.get("stream"):
             raise ValueError("logprobs are not available with stream")
         validate_processors(params, self.model_config.vocab_size if self.model_config else 1 << 31)     # normalises logit_bias to {int: float}
+        resolve_adapter(params.get("adapter"), adapter_slots(self.config))     # an unknown name fails here, before dispatch
         with self._lock:
             # degraded with recovery on: hold the request with the parked in-flight ones (bounded)
             # until the stage is re-admitted (plan.md:430-436) -- checked under the
@@ -642,4 +644,4 @@ class MasterNode:
         return {"state": self.state, "model": self.model_spec, "num_shards": self.num_shards,
                 "stage_workers": self.stage_workers, "spare_workers": spares, "workers": reg,
                 "metrics": self.metrics.summary(), "pending_requests": len(self._tasks),
-                "recoveries": self.recoveries}
+                "recoveries": self.recoveries, "adapters": sorted(self.config.lora_modules)}

@@ -55,6 +55,9 @@ class BatchMeta:
     max_ctx_d: int = 0
     max_q_len_p: int = 0
     max_ctx_p: int = 0          # the prefill rows' longest context (the split-context kernel's eligibility)
+    # multi-LoRA (ops/lora.py LoraPlan): the step's per-token adapter slots and row plan, None when no
+    # row of the step has an adapter -- the forward is then exactly the one without the feature
+    lora: Optional[object] = None
 
 
 class KVCache:
@@ -146,6 +149,7 @@ class ModelStage:
         self.embed: Dict[str, torch.Tensor] = {}
         self.head: Dict[str, torch.Tensor] = {}
         self.kv: Optional[KVCache] = None
+        self.lora = None             # models/lora.py StageLora once load_lora() found adapters configured
         self.cos_sin = None
         if cfg.arch != "gpt2":
             self.cos_sin = ref.rope_cos_sin(cfg.head_dim, cfg.max_position, cfg.rope_theta, cfg.rope_scaling,
@@ -270,6 +274,20 @@ class ModelStage:
         quant.quantize_layers(self.layers)
         return self
 
+    def load_lora(self, ecfg) -> "ModelStage":
+        """The adapters of ``ecfg.lora_modules`` for this stage's layers (models/lora.py); refuses what
+        cannot run with them (ValueError)."""
+        from . import lora
+        self.lora = lora.build_stage_lora(self, ecfg)
+        return self
+
+    def _lora(self, y: torch.Tensor, x: torch.Tensor, layer: int, proj: str, meta: BatchMeta) -> torch.Tensor:
+        """The dense projection output ``y`` = x W^T with the adapter deltas of the step's rows."""
+        if self.lora is None:
+            raise RuntimeError("the step carries adapter rows but the stage has no adapters loaded")
+        w = self.lora.layers[layer - self.layer_start].get(proj)
+        return y if w is None else ops.lora.apply(y, x, w, meta.lora)
+
     @staticmethod
     def _nbytes(t) -> int:
         return t.nbytes() if hasattr(t, "scale") else t.numel() * t.element_size()
@@ -278,7 +296,7 @@ class ModelStage:
         n = sum(self._nbytes(t) for d in self.layers for t in d.values())
         n += sum(t.numel() * t.element_size() for t in self.embed.values())
         n += sum(t.numel() * t.element_size() for t in self.head.values())
-        return n
+        return n + (self.lora.nbytes() if self.lora is not None else 0)
 
     def allocate_kv(self, num_blocks: int, block_size: int) -> KVCache:
         cfg = self.cfg
@@ -352,7 +370,14 @@ class ModelStage:
                                            max_ctx=meta.max_ctx or None, workspace=meta.attn_workspace)
         return o.view(o.shape[0], self.q_size_local)
 
-    def _mlp(self, h: torch.Tensor, lw: Dict[str, torch.Tensor]) -> torch.Tensor:
+    def _mlp(self, h: torch.Tensor, lw: Dict[str, torch.Tensor], layer: int = 0,
+             meta: Optional[BatchMeta] = None) -> torch.Tensor:
+        if meta is not None and meta.lora is not None and not self.cfg.is_moe:
+            # adapter rows in the step: the gate|up delta must land before the activation, so the plain
+            # GEMM, the expand over both slices, then SwiGLU; the down projection materialised
+            gu = self._lora(ops.linear(h, lw["w_gate_up"]), h, layer, "w_gate_up", meta)
+            act = ops.silu_mul(gu)
+            return self._lora(ops.linear(act, lw["w_down"], defer=False), act, layer, "w_down", meta)
         if self.cfg.is_moe:
             out = ops.moe_forward(h, lw["router"], lw["experts_gate_up"], lw["experts_down"],
                                   self.cfg.experts_per_token, self.tp.expert_offset(self.cfg.num_experts))
@@ -405,7 +430,11 @@ class ModelStage:
                     else:
                         x, residual = ops.fused_add_rms_norm(h, residual, lw["attn_norm"], eps, quant_out=q8)
                     h = None
-                    qkv = ops.linear(x, lw["wqkv"], defer=knobs.K.defer_qkv and self.has(l, 1))
+                    if meta.lora is not None:
+                        # adapter rows in the step: dense projection output, then the adapter deltas
+                        qkv = self._lora(ops.linear(x, lw["wqkv"], defer=False), x, l, "wqkv", meta)
+                    else:
+                        qkv = ops.linear(x, lw["wqkv"], defer=knobs.K.defer_qkv and self.has(l, 1))
                     if not self.has(l, 1):
                         out_aux = self._dense(qkv)
                         break
@@ -418,7 +447,9 @@ class ModelStage:
                     a = a if a is not None else carry
                     # defer: a split-K o-projection's reduce is fused into the MLP half's add + RMSNorm
                     # (TP: row-parallel partial sums, all-reduced over the group)
-                    if self.tp.enabled:
+                    if meta.lora is not None:
+                        h = self._lora(ops.linear(a, lw["wo"], defer=False), a, l, "wo", meta)
+                    elif self.tp.enabled:
                         h = self.tp.all_reduce_(ops.linear(a, lw["wo"]))
                     else:
                         h = ops.linear(a, lw["wo"], defer=knobs.K.defer_o)
@@ -430,7 +461,7 @@ class ModelStage:
                 else:
                     x, residual = ops.fused_add_rms_norm(h, residual, lw["mlp_norm"], eps, quant_out=q8)
                 if self.has(l, 3) and self.has(l, 4):
-                    h = self._mlp(x, lw)
+                    h = self._mlp(x, lw, l, meta)
                 elif self.has(l, 3):                  # cut between the MLP halves: hand over the partial sum
                     out_aux = self._dense(self._mlp(x, lw))
                     h = None

@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import _ext, knobs
-from . import gemm, quant
+from . import gemm, lora, quant
 from . import reference as ref
 
 __all__ = [

@@ -574,3 +574,58 @@ def moe_mlp(x: torch.Tensor, w_gate_up: torch.Tensor, w_down: torch.Tensor,
         y = linear(silu_mul(gu), w_down[e])
         out.index_add_(0, tok, y.float() * topk_w[tok, slot].unsqueeze(1).float())
     return out.to(x.dtype)
+
+
+# ------------------------------------------------------------ multi-LoRA
+# Per-row adapters as an additive delta after a projection (the HIP kernels of csrc/kernels/lora.hip
+# compute the same thing; the CPU engine runs this).  The projection's base output is y0 = dtype(x W^T)
+# as the GEMM leaves it once materialised.  Row t carries adapter slot a = slot[t]; a row with
+# a = -1 is untouched.  For the others
+#     v[t, j] = dtype( sum_k x[t, k] A_a[j, k] )            f32 accumulation, one rounding
+#     d[t, n] = sum_j v[t, j] B_a[n, j]                      f32
+#     y[t, n] = dtype( f32(y0[t, n]) + scale_a d[t, n] )     one rounding
+# scale_a = lora_alpha / r (lora_alpha / sqrt(r) with use_rslora) stays an f32 per slot, applied in the
+# epilogue, never folded into B.  A packed projection (q|k|v with unequal widths under GQA, gate|up)
+# holds one LoRA module per slice over the same input: A is stacked to [slots, nslices * rp, K] (rp:
+# the rank zero-padded, LORA_RANK_PAD), B is [slots, N, rp] with row n from the module that owns
+# output column n, and column n takes the v slice of that module.  A module the adapter does not
+# target is a zero slice.
+LORA_TILE = 16            # rows of a row-plan tile
+LORA_MAX_RANK = 64
+
+
+def lora_rank_pad(rank: int) -> int:
+    """The stored rank: zero-padded to what the MFMA shapes take (32 or 64)."""
+    if not 1 <= rank <= LORA_MAX_RANK:
+        raise ValueError(f"LoRA rank must be in [1, {LORA_MAX_RANK}], got {rank}")
+    return 32 if rank <= 32 else 64
+
+
+def lora_scale(lora_alpha: float, rank: int, use_rslora: bool = False) -> float:
+    return float(lora_alpha) / (math.sqrt(rank) if use_rslora else rank)
+
+
+def lora_apply(y0: torch.Tensor, x: torch.Tensor, slot: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+               scale: torch.Tensor, slice_starts=(0,)) -> torch.Tensor:
+    """y0 [T, N] and x [T, K] in the engine's dtype, slot [T] int, a [slots, nslices * rp, K], b
+    [slots, N, rp], scale [slots] float32, slice_starts: first output column of every slice.  Returns
+    a new tensor; rows with slot -1 are copied bit for bit."""
+    t, n = y0.shape
+    rp = b.shape[-1]
+    starts = list(slice_starts) + [n]
+    if a.shape[1] != rp * (len(starts) - 1):
+        raise ValueError("lora_apply: A must stack one rp-row block per slice")
+    y = y0.clone()
+    slot = slot.to(torch.int64)
+    for s in sorted(set(slot.tolist())):
+        if s < 0:
+            continue
+        rows = (slot == s).nonzero().flatten()
+        xs = x.index_select(0, rows)
+        v = (xs.float() @ a[s].float().t()).to(x.dtype).float()          # [n_rows, nslices * rp]
+        d = torch.empty(rows.numel(), n, dtype=torch.float32, device=y0.device)
+        for i in range(len(starts) - 1):
+            c0, c1 = starts[i], starts[i + 1]
+            d[:, c0:c1] = v[:, i * rp:(i + 1) * rp] @ b[s, c0:c1].float().t()
+        y[rows] = (y0.index_select(0, rows).float() + scale[s].float() * d).to(y0.dtype)
+    return y

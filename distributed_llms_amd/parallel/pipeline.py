@@ -38,7 +38,9 @@ from ..engine.runner import StageRunner
 from ..engine.sampler import ids_message_len, sample_step, unpack_ids_message
 from ..engine.scheduler import Scheduler, Step
 from ..engine.logit_state import LogitState
-from ..engine.sequence import SamplingParams, Sequence, request_seed, validate_logprobs, validate_processors
+from ..engine.sequence import (SamplingParams, Sequence, request_seed, resolve_adapter, validate_logprobs,
+                               validate_processors)
+from ..models.lora import adapter_slots
 from ..utils.tracing import get_tracer
 from .comm import STOP, PendingIds, Transport
 
@@ -128,6 +130,7 @@ class PipelineDriver:
         if self.tp is not None:
             ecfg.check_tensor_parallel(self.tp.size)
         self._seed_rng = random.Random(os.urandom(16))     # seeds of sampled requests that bring none
+        self.adapter_slots = adapter_slots(ecfg)           # every stage loaded the same set (build_stage)
         self.step_id = 0
         self.num_steps = 0
         self.num_lookahead = 0
@@ -140,7 +143,8 @@ class PipelineDriver:
             raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
         if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
             raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
-        seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id)
+        seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id,
+                       lora_slot=resolve_adapter(params.adapter, self.adapter_slots))
         seq.seed = request_seed(seq.params, self._seed_rng)
         self.scheduler.add(seq)
         return seq

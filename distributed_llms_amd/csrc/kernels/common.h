@@ -36,9 +36,18 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// max(m, a) of two values with a clear sign bit (|x|, 0, +Inf or a NaN after fabsf) that keeps a NaN
+// from either side (fmaxf drops it): the running |x| maximum of the FP8 row quantizers, where a NaN
+// or Inf element must reach the row's scale (see fp8_row_scale).  For such values the unsigned order
+// of the bit patterns is the numeric order, and every NaN pattern lies above +Inf: one v_max_u32.
+__device__ __forceinline__ float nan_max(float m, float a) {
+  return __uint_as_float(max(__float_as_uint(m), __float_as_uint(a)));
+}
+
+// Wave-wide nan_max (values with a clear sign bit): its only users are the FP8 row scales
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, DLLM_WAVE));
+  for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, DLLM_WAVE));
   return v;
 }
 
@@ -84,22 +93,27 @@ __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_r
 __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 
-// Block-wide max for blockDim.x <= 1024; `red` must hold >= 16 floats.
+// Block-wide max for blockDim.x <= 1024; `red` must hold >= 16 floats.  nan_max semantics: values
+// with a clear sign bit, and a NaN is kept.
 __device__ __forceinline__ float block_max(float v, float* red) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
   v = wave_max(v);
   if (lane == 0) red[wid] = v;
   __syncthreads();
   float t = red[0];
-  for (int i = 1; i < nw; ++i) t = fmaxf(t, red[i]);
+  for (int i = 1; i < nw; ++i) t = nan_max(t, red[i]);
   __syncthreads();
   return t;
 }
 
 // ---- per-token FP8 (OCP e4m3) quantization shared by quant.hip and the fused norm epilogues:
 // scale = amax / 448 (1 for an all-zero row), q = RNE(clamp(v / scale)), packed 4 per dword.
+// Non-finite rows: a row with a NaN or +-Inf element gets a non-finite scale (NaN gives NaN, Inf
+// gives Inf or NaN), so every output of that row in the following GEMM (acc * sa[m] * sb[n]) is
+// non-finite, as in the bf16 path; the row's q bytes are unspecified and every other row is
+// bit-identical to the run without the bad element.  The amax steps use nan_max for this.
 constexpr float kFp8Max = 448.f;
-__device__ __forceinline__ float fp8_row_scale(float amax) { return amax > 0.f ? amax / kFp8Max : 1.f; }
+__device__ __forceinline__ float fp8_row_scale(float amax) { return amax == 0.f ? 1.f : amax / kFp8Max; }
 __device__ __forceinline__ float fp8_in(float v, float s) { return fminf(fmaxf(v / s, -kFp8Max), kFp8Max); }
 __device__ __forceinline__ int pack4_fp8(float a, float b, float c, float d) {
   int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
@@ -131,7 +145,7 @@ __device__ __forceinline__ void norm_out_fp8(float (&v)[MAXV][8], float inv, con
       for (int j = 0; j < 8; ++j) {
         o[j] = f2bf(v[i][j] * inv * bf2f(g[j]));
         v[i][j] = bf2f(o[j]);
-        amax = fmaxf(amax, fabsf(v[i][j]));
+        amax = nan_max(amax, fabsf(v[i][j]));
       }
       if (y) reinterpret_cast<bf16x8*>(y)[idx] = o;
     }

@@ -7,6 +7,11 @@
 // (v_cvt_pk_fp8_f32) and 8-byte stores.  The GEMM multiplies its accumulator by
 // scale[m] * wscale[n] in the epilogue.  The RMSNorm kernels carry the same epilogue (q8 output)
 // for the projections that follow a norm; this kernel serves the o and down projection inputs.
+//
+// Non-finite rows: a row with a NaN or +-Inf element gets a non-finite scale[m] (NaN gives NaN, Inf
+// gives Inf or NaN; the amax is taken with nan_max, common.h).  Every output of that row in the
+// following GEMM is then non-finite, as in the bf16 path.  The row's q bytes are unspecified; every
+// other row is bit-identical to the run without the bad element.
 #include "common.h"
 #include "launchers.h"
 
@@ -31,7 +36,7 @@ __global__ void __launch_bounds__(256) quant_fp8_rows_kernel(uint8_t* __restrict
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           v[i][j] = bf2f(a[j]);
-          amax = fmaxf(amax, fabsf(v[i][j]));
+          amax = nan_max(amax, fabsf(v[i][j]));
         }
       }
     }
@@ -46,7 +51,7 @@ __global__ void __launch_bounds__(256) quant_fp8_rows_kernel(uint8_t* __restrict
     for (int idx = tid; idx < nvec; idx += 256) {
       const bf16x8 a = xr[idx];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(bf2f(a[j])));
+      for (int j = 0; j < 8; ++j) amax = nan_max(amax, fabsf(bf2f(a[j])));
     }
     const float s = fp8_row_scale(block_max(amax, red));
     if (tid == 0) scale[m] = s;

@@ -16,6 +16,12 @@ the bf16 ridge at batch 256 -- get both halves of their bound cut:
 Mixtral experts take the same scheme through the grouped kernel (``moe_wide_gemm_fp8``: fp8 token
 rows gathered by the expert-sorted slot list, per-(expert, channel) weight scales).
 
+Non-finite activations: a row with a NaN or +-Inf element gets a non-finite ``scale[m]`` (NaN
+gives NaN, Inf gives Inf or NaN).  Every output of that row in the following GEMM is then
+non-finite, as in the bf16 path.  The row's ``q`` bytes are unspecified; every other row is
+bit-identical to the run without the bad element.  The HIP quantizers (``quant_fp8_rows`` and the
+norm epilogues) and :func:`quantize_rows_ref` share this contract.
+
 Opt-in (``EngineConfig.quant = "fp8"``, ``bench.py --quant fp8``): the LM head, embeddings, norms,
 router, attention and the KV cache stay bf16.  CPU tensors take the PyTorch reference below (same
 quantization, f32 math), which is also the numerics oracle of the GPU tests.
@@ -133,8 +139,9 @@ class Fp8Act:
 
 def _absmax_scale(amax: torch.Tensor) -> torch.Tensor:
     # a tensor divisor: torch divides a GPU tensor by a Python scalar as a multiply by its
-    # (inexact) reciprocal; the kernel, and the CPU, divide correctly rounded
-    return torch.where(amax > 0, amax / torch.full_like(amax, FP8_MAX), torch.ones_like(amax))
+    # (inexact) reciprocal; the kernel, and the CPU, divide correctly rounded.  Only an all-zero row
+    # gets scale 1: a NaN or Inf amax (torch's amax propagates NaN) stays non-finite
+    return torch.where(amax == 0, torch.ones_like(amax), amax / torch.full_like(amax, FP8_MAX))
 
 
 def quantize_weight(w: torch.Tensor) -> Fp8Weight:
@@ -154,7 +161,8 @@ def quantize_experts(w: torch.Tensor) -> Fp8Experts:
 
 
 def quantize_rows_ref(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Per-row (per-token) absmax quantization, PyTorch reference: (q [M, K] e4m3, scale [M] f32)."""
+    """Per-row (per-token) absmax quantization, PyTorch reference: (q [M, K] e4m3, scale [M] f32).
+    A row with a NaN or Inf element gets a non-finite scale (module docstring)."""
     xf = x.reshape(-1, x.shape[-1]).float()
     s = _absmax_scale(xf.abs().amax(dim=1))
     return (xf / s[:, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8), s

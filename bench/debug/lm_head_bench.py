@@ -29,11 +29,11 @@ def main():
     it = [0]
     cands = {
         "pp_head (shipped)": lambda w: gemm.linear_pp(x, w, splits=1, variant=gemm.PP_HEAD_VARIANT),
-        "pp_sched2_default_policy": lambda w: gemm.linear_pp(x, w, splits=1, variant=64),
+        "pp_sched2_default_policy": lambda w: gemm.linear_pp(x, w, splits=1, variant=gemm.PP_SCHED2),
         "pf_static": lambda w: gemm.linear_pf(x, w),
-        "pf_dynamic": lambda w: gemm.linear_pf(x, w, variant=16),
-        "wide/sq": lambda w: gemm.linear_wide(x, w),
-        "pp_head_128col": lambda w: gemm.linear_pp(x, w, splits=1, variant=gemm.PP_HEAD_VARIANT | 1),
+        "pf_dynamic": lambda w: gemm.linear_pf(x, w, variant=gemm.PF_DYNAMIC),
+        "wide/sq": lambda w: gemm.linear_sq(x, w),                   # M = 256: the decode range's unsplit gemm_sq grid
+        "pp_head_128col": lambda w: gemm.linear_pp(x, w, splits=1, variant=gemm.PP_HEAD_VARIANT | gemm.PP_BN128),
     }
     res = {c: [] for c in cands}
     for fn in cands.values():

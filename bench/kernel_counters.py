@@ -44,7 +44,7 @@ def main():
         if want("gate_up"):
             gemm.linear_wide(bf(m, h, sc=0.5), bf(2 * inter, h, sc=0.02), swiglu=True)
         if want("lm_head"):
-            gemm.linear_wide(bf(m, h, sc=0.5), bf(128256, h, sc=0.02))
+            gemm.linear_sq(bf(m, h, sc=0.5), bf(128256, h, sc=0.02))    # the decode range's unsplit gemm_sq grid
         if want("norm"):
             ops.fused_add_rms_norm(bf(m, h), bf(m, h), bf(h), 1e-5)
         if want("silu"):

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launch_host.h"
 #include "launchers.h"
 
 
@@ -1377,12 +1378,6 @@ __global__ void __launch_bounds__(kW32Waves * 64, 1) attn_prefill_w32p_kernel(
 }
 
 // ------------------------------------------------------------------ launchers
-// f(std::integral_constant<int, V>{}) for the one V of Vs that equals v: a runtime value picks a template argument
-template <int... Vs, typename F>
-static void dispatch_value(int v, const char* what, F&& f) {
-  if (!((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...)) throw std::runtime_error(what);
-}
-
 // the GQA group sizes the prefill kernels are built for
 template <typename F>
 static void dispatch_group(int g, F&& f) {

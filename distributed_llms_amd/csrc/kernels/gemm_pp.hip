@@ -27,6 +27,7 @@
 //  * SwiGLU without a weight permutation: the B tile's 16-row groups alternate gate / up rows of
 //    the fused [2I, K] weight, so gate and up of an output column meet in one lane.
 #include "common.h"
+#include "launch_host.h"
 #include "launchers.h"
 
 #include <atomic>
@@ -628,26 +629,18 @@ int gemm_pp(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats,
             int mode, int variant, uintptr_t stream) {
   DLLM_HOST_CHECK(M >= 1, "M >= 1");
   DLLM_HOST_CHECK(K % PBK == 0 && K >= PBK, "K must be a positive multiple of 64");
-  DLLM_HOST_CHECK(mode == 0 || mode == 1 || mode == 2, "mode");
-  DLLM_HOST_CHECK(splits >= 1, "splits >= 1");
   const int BN = (variant & 1) ? 128 : 256;
-  const bool swiglu = mode == 1;
   DLLM_HOST_CHECK(N % BN == 0, "N must be a multiple of the column tile (128 / 256)");
+  const SplitK sk = splitk_plan(K, PBK, splits, mode);
+  const int S = sk.S;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int ksteps = K / PBK;
-  const int kps = (ksteps + splits - 1) / splits;
-  const int S = (ksteps + kps - 1) / kps;
-  DLLM_HOST_CHECK(mode != 2 || S > 1, "mode 2 needs a K split");
   const int mtiles = (M + 255) / 256;
   const long grid = (long)(N / BN) * mtiles * S;
   DLLM_HOST_CHECK((long)M * K * 2 < (1L << 32) && (long)N * K * 2 < (1L << 32), "operands must be < 4 GiB");
   DLLM_HOST_CHECK(grid >= 1 && grid < (1L << 31), "grid");
+  splitk_check_ws(sk, ws, ws_floats, M, N);
   const bool nt = (variant & 2) != 0;
   const bool grp = (variant & 4) != 0 && S == 1 && mtiles > 1;
-#define DLLM_PP_GO(BN_, MODE_, VAR_)                                                                     \
-  hipLaunchKernelGGL((gemm_pp_kernel<BN_, MODE_, VAR_>), dim3((unsigned)grid), dim3(256), 0, s, (const bf16*)a, \
-                     (const bf16*)b, (bf16*)c, (float*)ws, M, N, K, kps, S, dbg, (const int*)nullptr,       \
-                     (const int*)nullptr, (const int*)nullptr, 0)
   // variant bit 6: schedule 2 (the K-tile's fragments read early, staging spread; weights
   // nontemporal with bit 1 only in the natural tile order).  Bit 3: diagnostic build -- per-wave cycle stamps (loop, B_t waits) into the LAST
   // grid x 512 floats of ws (after the slabs); output as usual.  With it (schedule 1 only), bit 4:
@@ -660,38 +653,21 @@ int gemm_pp(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats,
     DLLM_HOST_CHECK(ws != 0 && grid * 512 + (S > 1 ? (long)S * M * N : 0) <= ws_floats, "profile build: ws too small");
     dbg = (float*)ws + (ws_floats - grid * 512);
   }
-#define DLLM_PP_V(BN_, MODE_)                                        \
-  do {                                                               \
-    if (sched2) {                                                    \
-      if (prof) { if (grp) DLLM_PP_GO(BN_, MODE_, 38); else DLLM_PP_GO(BN_, MODE_, 36); } \
-      else if (grp) DLLM_PP_GO(BN_, MODE_, 34);                      \
-      else if (nt) DLLM_PP_GO(BN_, MODE_, 33);                       \
-      else DLLM_PP_GO(BN_, MODE_, 32);                               \
-    } else if (prof) {                                               \
-      if (grp) DLLM_PP_GO(BN_, MODE_, 6);                            \
-      else if (variant & 16) DLLM_PP_GO(BN_, MODE_, 12);             \
-      else if (variant & 32) DLLM_PP_GO(BN_, MODE_, 20);             \
-      else DLLM_PP_GO(BN_, MODE_, 4);                                \
-    }                                                                \
-    else if (grp) { if (nt) DLLM_PP_GO(BN_, MODE_, 3); else DLLM_PP_GO(BN_, MODE_, 2); } \
-    else { if (nt) DLLM_PP_GO(BN_, MODE_, 1); else DLLM_PP_GO(BN_, MODE_, 0); }     \
-  } while (0)
-  if (S == 1) {
-    if (BN == 256) { if (swiglu) DLLM_PP_V(256, 2); else DLLM_PP_V(256, 0); }
-    else { if (swiglu) DLLM_PP_V(128, 2); else DLLM_PP_V(128, 0); }
-    DLLM_HIP_CHECK(hipGetLastError());
-    return 1;
-  }
-  DLLM_HOST_CHECK(ws != 0 && (long)S * M * N <= ws_floats, "split-K workspace too small");
-  // split: natural column order slabs (a SwiGLU is applied by the reduce)
-  if (BN == 256) DLLM_PP_V(256, 1);
-  else DLLM_PP_V(128, 1);
-#undef DLLM_PP_V
-#undef DLLM_PP_GO
-  DLLM_HIP_CHECK(hipGetLastError());
-  if (mode == 2) return S;
-  splitk_reduce_ex(c, ws, 0, S, M, N, swiglu ? 1 : 0, stream);
-  return S;
+  // the kernel's VAR: bit 0 weights nt, bit 1 grouped order, bit 2 profile (+ 8 / 16: its ablations), bit 5 schedule 2
+  const int VAR = sched2 ? (prof ? (grp ? 38 : 36) : grp ? 34 : nt ? 33 : 32)
+                : prof   ? (grp ? 6 : (variant & 16) ? 12 : (variant & 32) ? 20 : 4)
+                         : (grp ? 2 : 0) + (nt ? 1 : 0);
+  // the kernel's MODE: 0 plain, 2 SwiGLU; 1 = a K split: natural column order slabs (a SwiGLU is applied by the reduce)
+  dispatch_value<0, 1, 2>(S > 1 ? 1 : mode == 1 ? 2 : 0, "mode", [&](auto km) {
+    dispatch_value<256, 128>(BN, "column tile", [&](auto bn) {
+      dispatch_value<0, 1, 2, 3, 4, 6, 12, 20, 32, 33, 34, 36, 38>(VAR, "variant", [&](auto var) {
+        hipLaunchKernelGGL((gemm_pp_kernel<decltype(bn)::value, decltype(km)::value, decltype(var)::value>),
+                           dim3((unsigned)grid), dim3(256), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)c, (float*)ws, M,
+                           N, K, sk.kts, S, dbg, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, 0);
+      });
+    });
+  });
+  return splitk_finish(sk, c, ws, M, N, mode, stream);
 }
 
 // Grouped expert GEMM over the expert-sorted slot space (MoE prefill): expert e owns

@@ -24,6 +24,7 @@
 //  * split-K: f16 x 2^-6 partial slabs in natural column order (common.h), reduced by
 //    splitk_reduce(_swiglu) or deferred into splitk_add_rms_norm.
 #include "common.h"
+#include "launch_host.h"
 #include "launchers.h"
 
 #include <type_traits>
@@ -204,37 +205,31 @@ int gemm_sq(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats,
   DLLM_HOST_CHECK(M >= 1 && M <= 4 * QBM, "1 <= M <= 1024");
   DLLM_HOST_CHECK(K % QBK == 0, "K must be a multiple of 64");
   DLLM_HOST_CHECK(N % QBN == 0, "N must be a multiple of 256");
-  DLLM_HOST_CHECK(mode == 0 || mode == 1 || mode == 2, "mode");
-  DLLM_HOST_CHECK(splits >= 1, "splits >= 1");
+  const SplitK sk = splitk_plan(K, QBK, splits, mode);
+  const int S = sk.S;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int ktiles = K / QBK;
-  const int kts = (ktiles + splits - 1) / splits;
-  const int S = (ktiles + kts - 1) / kts;
-  DLLM_HOST_CHECK(mode != 2 || S > 1, "mode 2 needs a K split");
   const int mtiles = (M + QBM - 1) / QBM;
   const long grid = (long)(N / QBN) * mtiles * S;
   DLLM_HOST_CHECK(grid >= 1 && grid < (1L << 31), "grid");
-#define DLLM_SQ_GO(SPLIT_, SW_, V_)                                                                        \
-  hipLaunchKernelGGL((gemm_sq_kernel<SPLIT_, SW_, V_>), dim3((unsigned)grid), dim3(512), 0, s, (const bf16*)a, \
-                     (const bf16*)b, (bf16*)c, (float*)ws, M, N, K, kts, S)
+  splitk_check_ws(sk, ws, ws_floats, M, N);
   const bool early = variant & 4;
-  if (S == 1) {
-    if (mode == 1) { if (early) DLLM_SQ_GO(false, true, 6); else DLLM_SQ_GO(false, true, 2); }
-    else { if (early) DLLM_SQ_GO(false, false, 6); else DLLM_SQ_GO(false, false, 2); }
-    DLLM_HIP_CHECK(hipGetLastError());
-    return 1;
-  }
-  DLLM_HOST_CHECK(ws != 0 && (long)S * M * N <= ws_floats, "split-K workspace too small");
-  // split: natural column order (the SwiGLU, if any, is applied by the reduce)
-  if (variant == 12) DLLM_SQ_GO(true, false, 13);        // ablations (A/B only)
-  else if (variant == 20) DLLM_SQ_GO(true, false, 21);
-  else if (early) DLLM_SQ_GO(true, false, 5);
-  else DLLM_SQ_GO(true, false, 1);
-#undef DLLM_SQ_GO
-  DLLM_HIP_CHECK(hipGetLastError());
-  if (mode == 2) return S;
-  splitk_reduce_ex(c, ws, 0, S, M, N, mode == 1 ? 1 : 0, stream);
-  return S;
+  // unsplit: VAR 2, or 6 (early); split: natural column order slabs (the SwiGLU, if any, is applied by the
+  // reduce), VAR 1, 5 (early), or the ablations 13 / 21 (A/B only)
+  const int V = S == 1 ? (early ? 6 : 2) : variant == 12 ? 13 : variant == 20 ? 21 : early ? 5 : 1;
+  dispatch_value<0, 1>(S > 1, "split", [&](auto sp) {
+    constexpr bool SPLIT = decltype(sp)::value != 0;
+    auto go = [&](auto sw, auto v) {
+      hipLaunchKernelGGL((gemm_sq_kernel<SPLIT, decltype(sw)::value != 0, decltype(v)::value>), dim3((unsigned)grid),
+                         dim3(512), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)c, (float*)ws, M, N, K, sk.kts, S);
+    };
+    if constexpr (SPLIT)
+      dispatch_value<1, 5, 13, 21>(V, "variant", [&](auto v) { go(std::false_type{}, v); });
+    else
+      dispatch_value<0, 1>(mode == 1, "swiglu", [&](auto sw) {
+        dispatch_value<2, 6>(V, "variant", [&](auto v) { go(sw, v); });
+      });
+  });
+  return splitk_finish(sk, c, ws, M, N, mode, stream);
 }
 
 }  // namespace dllm

@@ -36,6 +36,7 @@
 // no LDS reads = same time, no barrier = same time, no staging loads = -21 % -- the loop is bound
 // by the load pipeline with a ~50 %-busy MFMA phase behind it.
 #include "common.h"
+#include "launch_host.h"
 #include "launchers.h"
 
 #include <type_traits>
@@ -678,6 +679,30 @@ static int wide_bm(int M) {
   return 256;
 }
 
+// The row tile of gemm_wide / gemm_wide_fp8: variant bits 8.. hold an optional override (stripped from
+// `variant` here), else the smallest of 64 / 128 / 192 / 256 that covers M, or 192 for 256 < M <= 384 (two
+// 192-row tiles instead of a half-empty second 256-row tile)
+static int wide_row_tile(int M, int& variant) {
+  const int bm_force = variant >> 8;
+  variant &= 0xff;
+  DLLM_HOST_CHECK(bm_force == 0 || bm_force == 64 || bm_force == 128 || bm_force == 192 || bm_force == 256,
+                  "row tile override must be 64, 128, 192 or 256");
+  return bm_force ? bm_force : wide_bm(M);
+}
+
+// f(BM, SPLIT, SWIGLU, V as integral constants) for the runtime values: the ladder of both wide launchers
+// (V = 65, the grouped row-tile order, is only asked for on unsplit grids)
+template <int... Vs, typename F>
+static void wide_dispatch(int BM, bool split, bool swiglu, int V, F&& f) {
+  dispatch_value<64, 128, 192, 256>(BM, "row tile", [&](auto bm) {
+    dispatch_value<0, 1>(split, "split", [&](auto sp) {
+      dispatch_value<0, 1>(swiglu, "swiglu", [&](auto sw) {
+        dispatch_value<Vs...>(V, "variant", [&](auto v) { f(bm, sp, sw, v); });
+      });
+    });
+  });
+}
+
 // mode 0: C = A B^T;  mode 1: SwiGLU, C[M, N/2] = silu(A Bg^T) * (A Bu^T) with B = [Bg; Bu];
 // mode 2: leave split-K partial slabs in ws (no reduce; S > 1 required).
 // Returns the effective number of K slices S (the partial slabs a deferred reduce must sum).
@@ -685,28 +710,17 @@ int gemm_wide(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_float
               int mode, int variant, uintptr_t stream) {
   DLLM_HOST_CHECK(M >= 1, "M >= 1");
   DLLM_HOST_CHECK(K % WBK == 0, "K must be a multiple of 64");
-  DLLM_HOST_CHECK(mode == 0 || mode == 1 || mode == 2, "mode");
+  DLLM_HOST_CHECK(N % 128 == 0, "N must be a multiple of 128");
+  const int BM = wide_row_tile(M, variant);
+  const SplitK sk = splitk_plan(K, WBK, splits, mode);
+  const int S = sk.S;
   const bool swiglu = mode == 1;
-  DLLM_HOST_CHECK(swiglu ? (N % 128 == 0) : (N % WBN == 0), "N must be a multiple of 128");
-  DLLM_HOST_CHECK(splits >= 1, "splits >= 1");
-  // variant bits 8..: optional row tile override (64 / 128 / 192 / 256), 0 = wide_bm(M)
-  const int bm_force = variant >> 8;
-  variant &= 0xff;
-  DLLM_HOST_CHECK(bm_force == 0 || bm_force == 64 || bm_force == 128 || bm_force == 192 || bm_force == 256,
-                  "row tile override must be 64, 128, 192 or 256");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int ktiles = K / WBK;
-  const int kts = (ktiles + splits - 1) / splits;
-  const int S = (ktiles + kts - 1) / kts;
-  DLLM_HOST_CHECK(mode != 2 || S > 1, "mode 2 needs a K split");
-  // row tile: the smallest of 64 / 128 / 192 / 256 that covers M, or 192 for 256 < M <= 384
-  // (two 192-row tiles instead of a half-empty second 256-row tile)
-  const int BM = bm_force ? bm_force : wide_bm(M);
   const int mtiles = (M + BM - 1) / BM;
   const int ntiles = swiglu ? (N / 2) / 64 : N / WBN;
   const long grid = (long)ntiles * mtiles * S;
   DLLM_HOST_CHECK(grid >= 1 && grid < (1L << 31), "grid");
-  if (S > 1) DLLM_HOST_CHECK(ws != 0 && (long)S * M * N <= ws_floats, "split-K workspace too small");
+  splitk_check_ws(sk, ws, ws_floats, M, N);
 
   // weights nt (variant 2) where the grid has no K split: -3..-5 % on the MLP up projection from
   // cold caches; on the split-K grids nt costs up to +25 % at M = 128 (profiles/wide_gemm.md)
@@ -719,40 +733,17 @@ int gemm_wide(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_float
   variant &= 7;
   if (variant == 1 && S == 1) variant = grp ? 1 : 2;
   else if (variant == 4) variant = 1;
-#define DLLM_WIDE_GO3(BM_, SPLIT_, SW_, V_)                                                                      \
-  hipLaunchKernelGGL((gemm_wide_kernel<BM_, SPLIT_, SW_, 3, V_>), dim3((unsigned)grid), dim3(512), 0, s,          \
-                     (const bf16*)a, (const bf16*)b, (bf16*)c, (float*)ws, M, N, K, kts, S)
-#define DLLM_WIDE_GO(BM_, SPLIT_, SW_)                                                                          \
-  do {                                                                                                         \
-    if (abl == 8) { if (variant == 2) DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 10); else DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 9); } \
-    else if (abl == 16) { if (variant == 2) DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 18); else DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 17); } \
-    else if (pf && abl == 32) { if (variant == 2) DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 162); else DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 161); } \
-    else if (pf) { if (variant == 2) DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 130); else DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 129); } \
-    else if (abl == 32) { if (variant == 2) DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 34); else DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 33); } \
-    else if (grp && !SPLIT_) DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 65);                                              \
-    else if (variant == 0) DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 0);                                                 \
-    else if (variant == 2) DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 2);                                                 \
-    else if (variant == 3) DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 3);                                                 \
-    else DLLM_WIDE_GO3(BM_, SPLIT_, SW_, 1);                                                                   \
-  } while (0)
-  if (S == 1) {
-    if (BM == 64) { if (swiglu) DLLM_WIDE_GO(64, false, true); else DLLM_WIDE_GO(64, false, false); }
-    else if (BM == 128) { if (swiglu) DLLM_WIDE_GO(128, false, true); else DLLM_WIDE_GO(128, false, false); }
-    else if (BM == 192) { if (swiglu) DLLM_WIDE_GO(192, false, true); else DLLM_WIDE_GO(192, false, false); }
-    else { if (swiglu) DLLM_WIDE_GO(256, false, true); else DLLM_WIDE_GO(256, false, false); }
-    DLLM_HIP_CHECK(hipGetLastError());
-    return 1;
-  }
-  if (BM == 64) { if (swiglu) DLLM_WIDE_GO(64, true, true); else DLLM_WIDE_GO(64, true, false); }
-  else if (BM == 128) { if (swiglu) DLLM_WIDE_GO(128, true, true); else DLLM_WIDE_GO(128, true, false); }
-  else if (BM == 192) { if (swiglu) DLLM_WIDE_GO(192, true, true); else DLLM_WIDE_GO(192, true, false); }
-  else { if (swiglu) DLLM_WIDE_GO(256, true, true); else DLLM_WIDE_GO(256, true, false); }
-#undef DLLM_WIDE_GO
-#undef DLLM_WIDE_GO3
-  DLLM_HIP_CHECK(hipGetLastError());
-  if (mode == 2) return S;
-  splitk_reduce_ex(c, ws, 0, S, M, N, swiglu ? 1 : 0, stream);
-  return S;
+  // the kernel's VAR: policy 1 or 2 (weights nt) under an ablation / prefetch / fragment-wait bit, else the
+  // grouped order, else policy 0 .. 3
+  const int nt = variant == 2;
+  const int V = abl == 8 ? 9 + nt : abl == 16 ? 17 + nt : pf && abl == 32 ? 161 + nt : pf ? 129 + nt
+              : abl == 32 ? 33 + nt : grp ? 65 : variant == 0 || variant == 3 ? variant : 1 + nt;
+  wide_dispatch<0, 1, 2, 3, 9, 10, 17, 18, 33, 34, 65, 129, 130, 161, 162>(BM, S > 1, swiglu, V, [&](auto bm, auto sp, auto sw, auto v) {
+    constexpr bool SPLIT = decltype(sp)::value != 0, SW = decltype(sw)::value != 0;
+    hipLaunchKernelGGL((gemm_wide_kernel<decltype(bm)::value, SPLIT, SW, 3, decltype(v)::value>), dim3((unsigned)grid),
+                       dim3(512), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)c, (float*)ws, M, N, K, sk.kts, S);
+  });
+  return splitk_finish(sk, c, ws, M, N, mode, stream);
 }
 
 // FP8 W8A8 wide GEMM: modes as gemm_wide; K in elements (= bytes), multiple of 128.
@@ -760,58 +751,29 @@ int gemm_wide_fp8(uintptr_t c, uintptr_t a, uintptr_t a_scale, uintptr_t b, uint
                   long ws_floats, int M, int N, int K, int splits, int mode, int variant, uintptr_t stream) {
   DLLM_HOST_CHECK(M >= 1, "M >= 1");
   DLLM_HOST_CHECK(K % 128 == 0, "fp8 K must be a multiple of 128");
-  DLLM_HOST_CHECK(mode == 0 || mode == 1 || mode == 2, "mode");
   DLLM_HOST_CHECK(a_scale != 0 && b_scale != 0, "fp8 GEMM needs both scale vectors");
-  const bool swiglu = mode == 1;
   DLLM_HOST_CHECK(N % 128 == 0, "N must be a multiple of 128");
-  DLLM_HOST_CHECK(splits >= 1, "splits >= 1");
-  const int bm_force = variant >> 8;
-  variant &= 0xff;
-  DLLM_HOST_CHECK(bm_force == 0 || bm_force == 64 || bm_force == 128 || bm_force == 192 || bm_force == 256,
-                  "row tile override must be 64, 128, 192 or 256");
+  const int BM = wide_row_tile(M, variant);
+  const SplitK sk = splitk_plan(K, 128, splits, mode);
+  const int S = sk.S;
+  const bool swiglu = mode == 1;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int ktiles = K / 128;
-  const int kts = (ktiles + splits - 1) / splits;
-  const int S = (ktiles + kts - 1) / kts;
-  DLLM_HOST_CHECK(mode != 2 || S > 1, "mode 2 needs a K split");
-  const int BM = bm_force ? bm_force : wide_bm(M);
   const int mtiles = (M + BM - 1) / BM;
   const int ntiles = swiglu ? (N / 2) / 64 : N / WBN;
   const long grid = (long)ntiles * mtiles * S;
   DLLM_HOST_CHECK(grid >= 1 && grid < (1L << 31), "grid");
-  if (S > 1) DLLM_HOST_CHECK(ws != 0 && (long)S * M * N <= ws_floats, "split-K workspace too small");
+  splitk_check_ws(sk, ws, ws_floats, M, N);
   // weights nt where the grid has no K split (as the bf16 kernel's variant 1); variant | 64: grouped
   // row-tile order for large M (no K split)
   const bool nt = (variant & 7) != 4 && S == 1;
   const bool grp = (variant & 64) != 0 && S == 1 && !nt;
-#define DLLM_F8_GO3(BM_, SPLIT_, SW_, V_)                                                                   \
-  hipLaunchKernelGGL((gemm_wide_fp8_kernel<BM_, SPLIT_, SW_, 3, V_>), dim3((unsigned)grid), dim3(512), 0, s,  \
-                     (const uint8_t*)a, (const uint8_t*)b, (const float*)a_scale, (const float*)b_scale,      \
-                     (bf16*)c, (float*)ws, M, N, K, kts, S)
-#define DLLM_F8_GO(BM_, SPLIT_, SW_)                                   \
-  do {                                                                \
-    if (nt) DLLM_F8_GO3(BM_, SPLIT_, SW_, 2);                          \
-    else if (grp && !SPLIT_) DLLM_F8_GO3(BM_, SPLIT_, SW_, 65);          \
-    else DLLM_F8_GO3(BM_, SPLIT_, SW_, 1);                              \
-  } while (0)
-  if (S == 1) {
-    if (BM == 64) { if (swiglu) DLLM_F8_GO(64, false, true); else DLLM_F8_GO(64, false, false); }
-    else if (BM == 128) { if (swiglu) DLLM_F8_GO(128, false, true); else DLLM_F8_GO(128, false, false); }
-    else if (BM == 192) { if (swiglu) DLLM_F8_GO(192, false, true); else DLLM_F8_GO(192, false, false); }
-    else { if (swiglu) DLLM_F8_GO(256, false, true); else DLLM_F8_GO(256, false, false); }
-    DLLM_HIP_CHECK(hipGetLastError());
-    return 1;
-  }
-  if (BM == 64) { if (swiglu) DLLM_F8_GO(64, true, true); else DLLM_F8_GO(64, true, false); }
-  else if (BM == 128) { if (swiglu) DLLM_F8_GO(128, true, true); else DLLM_F8_GO(128, true, false); }
-  else if (BM == 192) { if (swiglu) DLLM_F8_GO(192, true, true); else DLLM_F8_GO(192, true, false); }
-  else { if (swiglu) DLLM_F8_GO(256, true, true); else DLLM_F8_GO(256, true, false); }
-#undef DLLM_F8_GO
-#undef DLLM_F8_GO3
-  DLLM_HIP_CHECK(hipGetLastError());
-  if (mode == 2) return S;
-  splitk_reduce_ex(c, ws, 0, S, M, N, swiglu ? 1 : 0, stream);
-  return S;
+  wide_dispatch<1, 2, 65>(BM, S > 1, swiglu, nt ? 2 : grp ? 65 : 1, [&](auto bm, auto sp, auto sw, auto v) {
+    constexpr bool SPLIT = decltype(sp)::value != 0, SW = decltype(sw)::value != 0;
+    hipLaunchKernelGGL((gemm_wide_fp8_kernel<decltype(bm)::value, SPLIT, SW, 3, decltype(v)::value>),
+                       dim3((unsigned)grid), dim3(512), 0, s, (const uint8_t*)a, (const uint8_t*)b,
+                       (const float*)a_scale, (const float*)b_scale, (bf16*)c, (float*)ws, M, N, K, sk.kts, S);
+  });
+  return splitk_finish(sk, c, ws, M, N, mode, stream);
 }
 
 }  // namespace dllm

@@ -153,7 +153,7 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
         return quant.linear_fp8(x, w_gate_up, swiglu=True)
     if _gpu(x):
         y = gemm.linear_swiglu(x, w_gate_up)
-        if y is not None:
+        if y is not None:                    # None: gemm.route found no fused kernel (GemmRoute.unfused)
             return y
     return silu_mul(linear(x, w_gate_up))
 

@@ -195,7 +195,7 @@ def prefill_attn_version(max_q_len: int, head_dim: int) -> int:
         return v
     if head_dim != 128 or max_q_len < knobs.K.prefill_w32_min_q:
         return 4
-    return 7 if gemm._comm_cus else 9
+    return 7 if gemm.comm_cus() else 9
 
 
 def _prefill_plain_wgs(batch: int, num_kv_heads: int, max_q_len: int, group: int) -> int:

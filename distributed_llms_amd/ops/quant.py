@@ -33,6 +33,7 @@ from typing import Tuple
 import torch
 
 from .. import _ext, knobs
+from . import gemm
 
 FP8 = torch.float8_e4m3fn
 FP8_MAX = 448.0
@@ -204,15 +205,13 @@ def linear_ref(x, w: Fp8Weight, swiglu: bool = False) -> torch.Tensor:
 # (knobs.fp8_bm128)
 # prefill-sized M (no K split): grouped row-tile order (gemm_wide_fp8 variant bit 64) from this M:
 # at M = 32768 qkv 1018 -> 889 us, o 660 -> 599, gate|up 4509 -> 3924, down 2083 -> 1873 (1.8-2.0
-# PFLOP/s); at M = 2048 it is 1-6 % slower
 # PFLOP/s); at M = 2048 it is 1-6 % slower (knobs.fp8_group_m)
 
 
 def fp8_plan(m: int, n: int, k: int, swiglu: bool = False) -> Tuple[int, int]:
     """(K slices, row-tile override or 0) of gemm_wide_fp8 for this shape.  Default: the bf16
     kernel's rule on the 128-K tiles (a K-tile of fp8 holds the bytes of a 64-K bf16 tile)."""
-    from .gemm import wide_splits
-    s = wide_splits(m, n, k // 2, swiglu)
+    s = gemm.wide_splits(m, n, k // 2, swiglu)
     if knobs.K.fp8_bm128 and not swiglu and s > 1 and 128 < m <= 256:
         tiles = (n // 128) * 2
         return max(1, min(256 // tiles, (k // 128) // 4, 16)), 128
@@ -223,13 +222,23 @@ def fp8_splits(m: int, n: int, k: int, swiglu: bool = False) -> int:
     return fp8_plan(m, n, k, swiglu)[0]
 
 
+def fp8_route(m: int, n: int, k: int, swiglu: bool = False, splits: int = 0) -> gemm.GemmRoute:
+    """The route of gemm_wide_fp8: fp8_plan (``splits`` overrides it, on the default row tile) after
+    the workspace clamp; weights streamed nontemporal only where one row tile covers M (each weight
+    byte read once), the grouped row-tile order from knobs.fp8_group_m rows."""
+    s, bm = (splits, 0) if splits else fp8_plan(m, n, k, swiglu)
+    if m <= 256:
+        variant = gemm.FP8_NT
+    else:
+        variant = gemm.FP8_CACHED | (gemm.FP8_GROUPED if 0 < knobs.K.fp8_group_m <= m else 0)
+    return gemm.GemmRoute("wide", gemm.ws_splits(s, m, n), variant | bm << gemm.WIDE_ROW_TILE_SHIFT, swiglu)
+
+
 def linear_fp8(x: torch.Tensor, w: Fp8Weight, swiglu: bool = False, defer: bool = False, splits: int = 0):
     """y = x w^T (``swiglu``: silu(x Wg^T) * (x Wu^T), w = [Wg; Wu]) with W8A8 e4m3 operands.
     ``defer``: may return a :class:`~distributed_llms_amd.ops.gemm.SplitKPartial` (no SwiGLU)."""
     if not x.is_cuda:
         return linear_ref(x, w, swiglu)
-    from .gemm import SplitKPartial, _workspace
-    pre = isinstance(x, Fp8Act)
     k = x.shape[-1]
     n, kw = w.shape
     if kw != k:
@@ -238,31 +247,12 @@ def linear_fp8(x: torch.Tensor, w: Fp8Weight, swiglu: bool = False, defer: bool 
         raise ValueError("linear_fp8: N % 128 and K % 128")
     if x.dtype != torch.bfloat16:
         raise TypeError("linear_fp8: bf16 activations")
-    if pre:
+    if isinstance(x, Fp8Act):
         xq, xs = x.q, x.scale
-        m = xq.shape[0]
     else:
         x = x.contiguous()
-        m = x.numel() // k
         xq, xs = quantize_rows(x)
-    s, bm = fp8_plan(m, n, k, swiglu)
-    if splits:
-        s, bm = splits, 0
-    ws = _workspace(x.device)
-    if s > 1 and s * m * n > ws.numel():
-        s = max(1, ws.numel() // (m * n))
-    # weights streamed non-temporal only where one row tile covers M (each weight byte read once)
-    variant = (1 if m <= 256 else (4 | (64 if 0 < knobs.K.fp8_group_m <= m else 0))) | (bm << 8)
-    stream = torch.cuda.current_stream().cuda_stream
-    kern = _ext.kernels()
-    if defer and not swiglu and s > 1:
-        se = kern.gemm_wide_fp8(0, xq.data_ptr(), xs.data_ptr(), w.q.data_ptr(), w.scale.data_ptr(), ws.data_ptr(),
-                                ws.numel(), m, n, k, s, 2, variant, stream)
-        return SplitKPartial(ws, se, m, n, (*x.shape[:-1], n), x.dtype, x.device)
-    y = torch.empty(*x.shape[:-1], n // 2 if swiglu else n, dtype=x.dtype, device=x.device)
-    kern.gemm_wide_fp8(y.data_ptr(), xq.data_ptr(), xs.data_ptr(), w.q.data_ptr(), w.scale.data_ptr(), ws.data_ptr(),
-                       ws.numel(), m, n, k, s, 1 if swiglu else 0, variant, stream)
-    return y
+    return gemm._launch("gemm_wide_fp8", x, w, fp8_route(xq.shape[0], n, k, swiglu, splits), defer, (xq, xs))
 
 
 def moe_mlp_ref(x: torch.Tensor, w_gate_up: Fp8Experts, w_down: Fp8Experts, topk_w: torch.Tensor,

@@ -219,9 +219,18 @@ PP_SHAPES = [(1, 256, 64, 8, 1), (77, 512, 192, 8, 3), (257, 256, 320, 8, 2), (7
 # gemm_pf: (m, n, k, r, variant); N = 4096 at M = 4100 is 272 tiles on 256 CUs
 PF_CASES = [(m, 4096, 128, 8, 0) for m in (1, 255, 256, 257, 4100)] + [(77, 256, 64, 8, 0), (257, 512, 192, 8, 8)]
 PF_DYNAMIC_CASES = [(4100, 4096, 128, 8), (300, 512, 192, 8)]
-# ops.linear, one shape per branch of gemm.linear: (branch, m, n, k, r)
+# ops.linear, one shape per branch of gemm.linear: (branch, m, n, k, r).  The first three run a K split (the
+# smallest K that still splits); sq is the decode range's unsplit 256 x 256 grid (130 tiles), pp_head the
+# decode LM head (N > 65536), torch what no kernel takes (N % 256 above the decode range)
 DISPATCH_CASES = [("wide", 64, 256, 4096, 4), ("pp_down", 256, 256, 16384, 2), ("pp", 300, 512, 384, 8),
-                  ("pf", 4096, 4096, 128, 8)]
+                  ("pf", 4096, 4096, 128, 8), ("sq", 256, 33280, 128, 8), ("pp_head", 256, 65792, 128, 8),
+                  ("torch", 300, 4224, 128, 8)]
+DISPATCH_SPLIT = ("wide", "pp_down", "pp")
+# ops.linear_swiglu, one shape per branch of gemm.linear_swiglu: (branch, m, inter, k) -- decode gate|up on
+# gemm_pp's 128-column tile (128 tiles on 256 CUs) and on its 256-column tile (258 / 129 tiles), gemm_wide,
+# medium-M gemm_pp (2 K slices into the SwiGLU reduce) and gemm_pf
+SWIGLU_DISPATCH_CASES = [("pp128", 256, 8192, 128), ("pp256", 256, 16512, 128), ("wide", 64, 256, 128),
+                         ("pp", 300, 256, 384), ("pf", 4096, 2048, 128)]
 # splitk_add_rms_norm: (m, n, k, r, splits) with S == splits
 NORM_CASES = [(65, 1024, 128, 8, 2), (65, 4096, 512, 8, 8), (65, 1024, 1024, 4, 16), (129, 4096, 128, 8, 2)]
 # part C: partly filled row tiles; (n, k, r, splits)
@@ -250,5 +259,5 @@ def all_int_cases():
     out += NORM_CASES
     n, k, r, s = GUARD_SHAPE
     out += [(m, n, k, r, s) for m in GUARD_M] + [(4100, 512, 128, 8, 1), (257, 512, 128, 8, 1)]
-    out += [(m, n, k, r, s) for b, m, n, k, r in DISPATCH_CASES for s in ((1,) if b == "pf" else range(2, 17))]
+    out += [(m, n, k, r, s) for b, m, n, k, r in DISPATCH_CASES for s in (range(2, 17) if b in DISPATCH_SPLIT else (1,))]
     return sorted(set(out))

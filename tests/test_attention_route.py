@@ -42,14 +42,19 @@ def test_table_covers_the_grid(table):
     assert {r["exp_version"] for r in table} == {3, 4, 5, 7, 9}
 
 
-def test_prefill_route_reproduces_the_table(table, monkeypatch):
+def test_prefill_route_reproduces_the_table(table):
     for r in table:
-        monkeypatch.setattr(gemm, "_comm_cus", r["comm_cus"])
-        with knobs.override(prefill_attn=r["prefill_attn"], prefill_fused_rope=bool(r["prefill_fused_rope"]),
-                            prefill_split_min_ctx=r["prefill_split_min_ctx"]):
-            got = ops.prefill_route(r["batch"], r["num_heads"], r["num_kv_heads"], r["head_dim"], r["max_q_len"],
-                                    r["max_ctx"], r["max_blocks"], version=r["version"], nsplit=r["nsplit"],
-                                    allow_rope_in_kernel=bool(r["allow_rope_in_kernel"]))
+        if r["comm_cus"]:
+            gemm.reserve_cus_for_comm(r["comm_cus"])
+        try:
+            with knobs.override(prefill_attn=r["prefill_attn"], prefill_fused_rope=bool(r["prefill_fused_rope"]),
+                                prefill_split_min_ctx=r["prefill_split_min_ctx"]):
+                got = ops.prefill_route(r["batch"], r["num_heads"], r["num_kv_heads"], r["head_dim"], r["max_q_len"],
+                                        r["max_ctx"], r["max_blocks"], version=r["version"], nsplit=r["nsplit"],
+                                        allow_rope_in_kernel=bool(r["allow_rope_in_kernel"]))
+        finally:
+            if r["comm_cus"]:
+                gemm.release_cus_for_comm()
         want = ops.PrefillRoute(r["exp_version"], bool(r["exp_rope_in_kernel"]), r["exp_nsplit"], r["exp_split_chunks"])
         assert got == want, r
 

@@ -177,31 +177,65 @@ def test_pf_dynamic_queue_resets_itself(cuda, m, n, k, r):
     assert_bits(y2, c.expected)
 
 
-@pytest.mark.parametrize("branch,m,n,k,r", gx.DISPATCH_CASES)
-def test_dispatcher_shipped_defaults(cuda, monkeypatch, branch, m, n, k, r):
-    """ops.linear and ops.linear(defer=True) with the shipped knobs, one shape per branch of
-    gemm.linear: gemm_wide, the long-K down projection on split gemm_pp (pp_down_min_k), medium-M
-    gemm_pp, and gemm_pf."""
+@pytest.fixture
+def launches(monkeypatch):
+    """Every gemm_* launch the host path makes, as (function, variant), with the launch going through."""
     calls = []
-    for name in ("linear_wide", "linear_pp", "linear_pf"):
-        def spy(*a, _f=getattr(gemm, name), _n=name, **kw):
-            calls.append((_n, kw.get("variant")))
-            return _f(*a, **kw)
-        monkeypatch.setattr(gemm, name, spy)
+    kk = _ext.kernels()
+
+    class Spy:
+        def __getattr__(self, name):
+            f = getattr(kk, name)
+            if not name.startswith("gemm_"):
+                return f
+
+            def launcher(*a):                 # (..., mode, variant, stream) in every gemm_* launcher
+                calls.append((name, a[-2]))
+                return f(*a)
+            return launcher
+
+    spy = Spy()
+    monkeypatch.setattr(_ext, "kernels", lambda: spy)
+    return calls
+
+
+def assert_launches(calls, want, count):
+    """``want``: None (no launch), or (function, variant or None: whatever the knobs say)."""
+    assert [(f, v if want[1] is not None else None) for f, v in calls] == ([want] * count if want else []), calls
+
+
+@pytest.mark.parametrize("branch,m,n,k,r", gx.DISPATCH_CASES)
+def test_dispatcher_shipped_defaults(cuda, launches, branch, m, n, k, r):
+    """ops.linear and ops.linear(defer=True) with the shipped knobs, one shape per branch of
+    gemm.linear: the decode LM head on gemm_pp, the long-K down projection on split gemm_pp
+    (pp_down_min_k), gemm_wide, gemm_sq on its unsplit grid, medium-M gemm_pp, gemm_pf, and F.linear."""
     c = gx.int_case(m, n, k, r)
     x, w = c.x.cuda(), c.w.cuda()
-    for s in range(2, 17) if branch != "pf" else ():
+    for s in range(2, 17) if branch in gx.DISPATCH_SPLIT else ():
         gx.check_slabs(c, s)                              # whatever K split the dispatcher picks
     y = ops.linear(x, w)
     d = ops.linear(x, w, defer=True)
-    want = {"wide": ("linear_wide", None), "pp_down": ("linear_pp", 64 | 2 | 1),
-            "pp": ("linear_pp", gemm.PP_PREFILL_VARIANT), "pf": ("linear_pf", None)}[branch]
-    assert calls == [want, want], calls
-    if branch != "pf":
+    want = {"wide": ("gemm_wide", None), "pp_down": ("gemm_pp", gemm.PP_DOWN_VARIANT),
+            "pp": ("gemm_pp", gemm.PP_PREFILL_VARIANT), "pf": ("gemm_pf", None), "sq": ("gemm_sq", None),
+            "pp_head": ("gemm_pp", gemm.PP_HEAD_VARIANT), "torch": None}[branch]
+    assert_launches(launches, want, 2)
+    if branch in gx.DISPATCH_SPLIT:
         assert isinstance(d, gemm.SplitKPartial) and 1 < d.splits <= 16
         d = d.materialize()
     assert_bits(y, c.expected)
     assert_bits(d, c.expected)
+
+
+@pytest.mark.parametrize("branch,m,inter,k", gx.SWIGLU_DISPATCH_CASES)
+def test_swiglu_dispatcher_shipped_defaults(cuda, launches, branch, m, inter, k):
+    """ops.linear_swiglu with the shipped knobs, one shape per branch of gemm.linear_swiglu."""
+    c = gx.swiglu_case(m, inter, k)
+    y = ops.linear_swiglu(c.x.cuda(), c.w.cuda())
+    want = {"pp128": ("gemm_pp", gemm.PP_GATE_UP_VARIANT), "pp256": ("gemm_pp", gemm.PP_GATE_UP_VARIANT & ~gemm.PP_BN128),
+            "wide": ("gemm_wide", None), "pp": ("gemm_pp", gemm.PP_PREFILL_VARIANT), "pf": ("gemm_pf", None)}[branch]
+    assert_launches(launches, want, 1)
+    assert y.shape == (m, inter)
+    assert_swiglu(y, c.ref)
 
 
 def norm_reference(new_res, g, eps):

@@ -20,7 +20,7 @@ def _bf(*s, scale=1.0):
 def test_small_m_linear_dispatch(cuda, m, n, k):
     """Decode batches 1..64 take the wide kernel's 64-row tile through the default dispatch."""
     x, w = _bf(m, k), _bf(n, k, scale=0.05)
-    assert gemm._use_wide(m, n, k, x, w)
+    assert gemm._use_wide(m, n, k, x, w) and gemm.route(m, n, k).kernel == "wide"
     y = gemm.linear(x, w)
     ref = x.float() @ w.float().t()
     torch.testing.assert_close(y.float(), ref, atol=3e-2, rtol=3e-2)
@@ -46,7 +46,7 @@ def test_small_m_swiglu(cuda, m, inter, k):
 def test_large_m_uses_hand_written_prefill_gemm(cuda):
     x, w = _bf(300, 256), _bf(512, 256, scale=0.05)          # a qkv-like (N > K) projection
     assert not gemm._use_wide(300, 512, 256, x, w)
-    assert gemm._use_pp(300, 512, 256, x, w, gemm.knobs.K.pp_proj_min_m)
+    assert gemm._use_pp(300, 512, 256, x, w, gemm.knobs.K.pp_proj_min_m) and gemm.route(300, 512, 256).kernel == "pp"
     y = ops.linear(x, w)
     torch.testing.assert_close(y.float(), x.float() @ w.float().t(), atol=3e-2, rtol=3e-2)
 
@@ -400,3 +400,37 @@ def test_long_k_down_on_split_gemm_pp(cuda, m):
         d = d.materialize()
     torch.testing.assert_close(y.float(), ref, atol=3e-2, rtol=3e-2)
     torch.testing.assert_close(d.float(), ref, atol=3e-2, rtol=3e-2)
+
+
+@pytest.mark.parametrize("kern", ["gemm_wide", "gemm_wide_fp8", "gemm_pp", "gemm_sq"])
+def test_launcher_host_checks(cuda, kern):
+    """Every precondition the split-K launchers check on the host raises instead of launching: K or N off the
+    tile, splits = 0, an unknown mode, mode 2 without a K split, a workspace declared too small, and (the two
+    wide launchers, which have one) a row-tile override of 96.  Every buffer is real and sized for the next
+    valid shape up (M = 65, N = 512, K = 256, two slabs), so a check that went missing would launch inside
+    memory the test owns; only the declared workspace size is short."""
+    from distributed_llms_amd import _ext
+    m, n, k = 65, 256, 128
+    x, w, y = _bf(m, 2 * k), _bf(2 * n, 2 * k), _bf(m, 2 * n)
+    ws = torch.empty(2 * m * 2 * n, dtype=torch.float32, device="cuda")
+    sa, sb = torch.ones(m, device="cuda"), torch.ones(2 * n, device="cuda")
+    fn = getattr(_ext.kernels(), kern)
+    stream = torch.cuda.current_stream().cuda_stream
+    fp8 = kern == "gemm_wide_fp8"
+    kt = 128 if fp8 else 64
+
+    def launch(n=n, k=2 * kt, ws_floats=ws.numel(), splits=1, mode=0, variant=0):
+        ptrs = (x.data_ptr(), sa.data_ptr(), w.data_ptr(), sb.data_ptr()) if fp8 else (x.data_ptr(), w.data_ptr())
+        return fn(y.data_ptr(), *ptrs, ws.data_ptr(), ws_floats, m, n, k, splits, mode, variant, stream)
+
+    assert launch(splits=2) == 2                                    # the shape itself is fine
+    bad = [dict(k=kt + kt // 2), dict(n=n + 64), dict(splits=0), dict(mode=3), dict(splits=1, mode=2),
+           dict(splits=2, ws_floats=2 * m * n - 1), dict(splits=2, mode=2, ws_floats=2 * m * n - 1)]
+    if kern in ("gemm_wide", "gemm_wide_fp8"):
+        bad.append(dict(variant=1 | 96 << gemm.WIDE_ROW_TILE_SHIFT))
+    if kern == "gemm_pp":
+        bad.append(dict(n=n + 64, variant=gemm.PP_BN128))                       # its 128-column tile
+    for kw in bad:
+        with pytest.raises(RuntimeError, match="dllm kernel precondition"):
+            launch(**kw)
+    torch.cuda.synchronize()

@@ -1,11 +1,12 @@
-"""Decode GEMM routing between the wide-M HIP kernel (csrc/kernels/gemm_wide.hip) and hipBLASLt.
+"""Decode GEMM routing between the hand-written HIP kernels (gemm_wide, gemm_sq, gemm_pp, gemm_pf).
 
 The cutovers are measured in-engine (profiles/wide_gemm.md): gate|up (SwiGLU) and qkv / o on the
 wide kernel up to M = 256, the K >= 8192 down projection up to M = 512 (distributed_llms_amd/knobs.py).
-CPU-only: `_use_wide` is pure shape / dtype logic."""
+CPU-only: `gemm.route` and its predicates are pure shape / dtype logic."""
 import pytest
 import torch
 
+from distributed_llms_amd import knobs
 from distributed_llms_amd.ops import gemm
 
 
@@ -90,6 +91,8 @@ def test_sq_only_on_unsplit_grids():
     knobs.update(sq_split=True)
     assert gemm.use_sq(256, 4096, 14336)
     assert gemm.sq_splits(256, 4096, 14336) == 16 and gemm.sq_splits(256, 6144, 4096) == 10
+    assert gemm.route(256, 4096, 14336) == gemm.GemmRoute("sq", 16, knobs.K.sq_variant)
+    assert gemm.route(256, 6144, 4096) == gemm.GemmRoute("sq", 10, knobs.K.sq_variant)
 
 
 def test_knobs_move_the_cutovers_and_reject_unknown_names():
@@ -111,7 +114,7 @@ def test_knobs_move_the_cutovers_and_reject_unknown_names():
 def test_prefill_gemms_go_to_hand_written_kernels():
     """Every prefill projection above the decode ranges runs on the persistent schedule-2 kernel
     (gemm_pf): gate|up with the SwiGLU from knobs.pp_swiglu_min_m, qkv / o / down from
-    pp_proj_min_m -- hipBLASLt only for shapes none of the kernels takes (N % 256, a bias)."""
+    pp_proj_min_m -- torch's F.linear only for shapes none of the kernels takes (N % 256, a bias)."""
     from distributed_llms_amd import knobs
     x, w = _xw(32768, 28672, 4096)
     kn = knobs.K
@@ -121,8 +124,13 @@ def test_prefill_gemms_go_to_hand_written_kernels():
     assert gemm._use_pp(32768, 6144, 4096, x, w, kn.pp_proj_min_m)
     assert gemm._use_pp(32768, 4096, 14336, x, w, kn.pp_proj_min_m)
     assert not gemm._use_pp(32768, 28672 + 128, 4096, x, w, kn.pp_swiglu_min_m)   # N % 256
+    assert gemm.route(32768, 28672, 4096, True) == gemm.GemmRoute("pf", 0, 0, True)
+    assert gemm.route(32768, 6144, 4096) == gemm.route(32768, 4096, 14336) == gemm.GemmRoute("pf")
+    assert gemm.route(32768, 28672 + 128, 4096, True) == gemm.GemmRoute("torch", unfused=True)
+    assert gemm.route(32768, 6144, 4096, bias=True) == gemm.GemmRoute("torch")
     knobs.update(pp_swiglu_min_m=0)
     assert not gemm._use_pp(32768, 28672, 4096, x, w, knobs.K.pp_swiglu_min_m)
+    assert gemm.route(32768, 28672, 4096, True) == gemm.GemmRoute("pf", unfused=True)
 
 
 def test_decode_lm_head_goes_to_gemm_pp():
@@ -195,44 +203,27 @@ def test_decode_gate_up_on_gemm_pp_128_column_tile():
     """knobs.pp_gate_up_min_m: the 8B gate|up at 200 <= M <= 256 runs on gemm_pp's 128-column tile
     with nontemporal weights (224 tiles: one round), the 70B gate|up on its 256-column tile (224
     tiles); not below the cutover, not while comm kernels reserve CUs."""
-    from distributed_llms_amd.ops import gemm
-    calls = []
-    orig_pp, orig_wide, orig_sq = gemm.linear_pp, gemm.linear_wide, gemm.linear_sq
-    gemm.linear_pp = lambda *a, **k: calls.append(("pp", k.get("variant"), k.get("splits")))
-    gemm.linear_wide = lambda *a, **k: calls.append(("wide",))
-    gemm.linear_sq = lambda *a, **k: calls.append(("sq",))
+    r = [gemm.route(256, 28672, 4096, True), gemm.route(192, 28672, 4096, True), gemm.route(256, 57344, 8192, True),
+         gemm.route(256, 28672, 4096, True, comm_cus=16)]
+    gemm.reserve_cus_for_comm(16)
     try:
-        gemm.linear_swiglu(*_xw(256, 28672, 4096))
-        gemm.linear_swiglu(*_xw(192, 28672, 4096))
-        gemm.linear_swiglu(*_xw(256, 57344, 8192))
-        gemm.reserve_cus_for_comm(16)
-        try:
-            gemm.linear_swiglu(*_xw(256, 28672, 4096))
-        finally:
-            gemm.release_cus_for_comm()
+        assert gemm.route(256, 28672, 4096, True) == r[3]
     finally:
-        gemm.linear_pp, gemm.linear_wide, gemm.linear_sq = orig_pp, orig_wide, orig_sq
-    assert calls[0] == ("pp", gemm.PP_GATE_UP_VARIANT, 1)
-    assert calls[1][0] == "wide" and calls[3][0] == "wide"
-    assert calls[2] == ("pp", gemm.PP_GATE_UP_VARIANT & ~1, 1)       # 70B: 224 x 256-column tiles
+        gemm.release_cus_for_comm()
+    assert (r[0].kernel, r[0].variant, r[0].splits) == ("pp", gemm.PP_GATE_UP_VARIANT, 1) and r[0].swiglu
+    assert r[1].kernel == "wide" and r[3].kernel == "wide" and r[1].swiglu and r[3].swiglu
+    assert (r[2].kernel, r[2].variant, r[2].splits) == ("pp", gemm.PP_GATE_UP_VARIANT & ~1, 1)   # 70B: 224 x 256-column tiles
+    assert gemm.PP_GATE_UP_VARIANT & ~1 == gemm.PP_GATE_UP_VARIANT & ~gemm.PP_BN128 == gemm.PP_SCHED2 | gemm.PP_NT
 
 
 def test_long_k_down_on_split_gemm_pp():
     """knobs.pp_down_min_k: the 70B down projection (K = 28672) at decode M on split gemm_pp
     128-column tiles (64 tiles x 4 slices, nontemporal weights); the 8B down (K = 14336) and other
     projections keep gemm_wide."""
-    from distributed_llms_amd.ops import gemm
-    calls = []
-    orig_pp, orig_wide = gemm.linear_pp, gemm.linear_wide
-    gemm.linear_pp = lambda *a, **k: calls.append(("pp", k.get("splits"), k.get("variant")))
-    gemm.linear_wide = lambda *a, **k: calls.append(("wide",))
-    try:
-        gemm.linear(*_xw(256, 8192, 28672), defer=True)
-        gemm.linear(*_xw(256, 4096, 14336), defer=True)
-        gemm.linear(*_xw(128, 8192, 28672), defer=True)
-    finally:
-        gemm.linear_pp, gemm.linear_wide = orig_pp, orig_wide
-    assert calls == [("pp", 4, 64 | 2 | 1), ("wide",), ("wide",)]
+    r = [gemm.route(256, 8192, 28672), gemm.route(256, 4096, 14336), gemm.route(128, 8192, 28672)]
+    assert [(x.kernel, x.splits, x.variant) for x in r[:1]] == [("pp", 4, gemm.PP_DOWN_VARIANT)]
+    assert gemm.PP_DOWN_VARIANT == gemm.PP_SCHED2 | gemm.PP_NT | gemm.PP_BN128 == 67
+    assert [x.kernel for x in r] == ["pp", "wide", "wide"]
 
 
 def test_o_projection_runs_as_two_128_row_tiles_at_decode():
@@ -249,21 +240,16 @@ def test_o_projection_runs_as_two_128_row_tiles_at_decode():
 
 
 def test_lm_head_leaves_gemm_pp_while_comm_cus_are_reserved():
-    from distributed_llms_amd.ops import gemm
-    x, w = _xw(256, 128256, 4096)
-    assert gemm._use_pp(256, 128256, 4096, x, w, 1)
-    calls = []
-    orig_pp, orig_wide = gemm.linear_pp, gemm.linear_wide
-    gemm.linear_pp = lambda *a, **k: calls.append("pp")
-    gemm.linear_wide = lambda *a, **k: calls.append("wide")
+    """Beside comm kernels the decode LM head runs on gemm_sq's unsplit grid (knobs.head_beside_comm)."""
+    assert gemm._use_pp(256, 128256, 4096, *_xw(256, 128256, 4096), 1)
+    routes = [gemm.route(256, 128256, 4096)]
+    gemm.reserve_cus_for_comm(16)
     try:
-        gemm.linear(x, w)
-        gemm.reserve_cus_for_comm(16)
-        gemm.linear(x, w)
+        routes.append(gemm.route(256, 128256, 4096))
     finally:
         gemm.release_cus_for_comm()
-        gemm.linear_pp, gemm.linear_wide = orig_pp, orig_wide
-    assert calls == ["pp", "wide"]
+    assert [r.kernel for r in routes] == ["pp", "sq"]
+    assert routes[1] == gemm.route(256, 128256, 4096, comm_cus=16) == gemm.GemmRoute("sq", 1, knobs.K.sq_variant)
 
 
 def test_rope_in_kernel_gated_on_block_table_width():

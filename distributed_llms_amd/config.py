@@ -22,7 +22,7 @@ from typing import Any, Dict, Optional
 @dataclass
 class ModelConfig:
     name: str
-    arch: str                      # "llama" (Llama-2/3), "mixtral", "gpt2"
+    arch: str                      # "llama" (Llama-2/3, Qwen2/3 with the flags below), "mixtral", "gpt2"
     vocab_size: int
     hidden_size: int
     intermediate_size: int
@@ -39,6 +39,8 @@ class ModelConfig:
     experts_per_token: int = 0     # MoE top-k
     bos_token_id: int = 1
     eos_token_id: int = 2
+    attn_bias: bool = False        # Qwen2 / Qwen2.5: bias on the q, k and v projections
+    qk_norm: bool = False          # Qwen3: RMSNorm over head_dim on every q and k head, before RoPE
 
     # ------------------------------------------------------------------ sizes
     @property
@@ -70,6 +72,10 @@ class ModelConfig:
         else:
             mlp = 3 * h * i
             norms = 2 * h
+        if self.arch != "gpt2":
+            attn += self.qkv_size if self.attn_bias else 0
+            norms += 2 * self.head_dim if self.qk_norm else 0
+            attn += h if self.attn_bias and self.qk_norm else 0     # Qwen3 attention_bias: o_proj.bias
         return attn + mlp + norms
 
     def embed_param_count(self) -> int:
@@ -103,9 +109,14 @@ class ModelConfig:
                 "bos_token_id": self.bos_token_id, "eos_token_id": self.eos_token_id,
                 "activation_function": "gelu_new", "_dllm_name": self.name,
             }
+        if self.qk_norm:
+            mt, cls = "qwen3", "Qwen3ForCausalLM"
+        elif self.attn_bias:
+            mt, cls = "qwen2", "Qwen2ForCausalLM"
+        else:
+            mt, cls = ("mixtral", "MixtralForCausalLM") if self.is_moe else ("llama", "LlamaForCausalLM")
         d = {
-            "model_type": "mixtral" if self.is_moe else "llama",
-            "architectures": ["MixtralForCausalLM" if self.is_moe else "LlamaForCausalLM"],
+            "model_type": mt, "architectures": [cls],
             "vocab_size": self.vocab_size, "hidden_size": self.hidden_size,
             "intermediate_size": self.intermediate_size,
             "num_hidden_layers": self.num_layers, "num_attention_heads": self.num_heads,
@@ -117,6 +128,8 @@ class ModelConfig:
         }
         if self.rope_scaling:
             d["rope_scaling"] = dict(self.rope_scaling)
+        if self.qk_norm:
+            d["attention_bias"] = self.attn_bias
         if self.is_moe:
             d["num_local_experts"] = self.num_experts
             d["num_experts_per_tok"] = self.experts_per_token
@@ -138,8 +151,18 @@ class ModelConfig:
                 head_dim=h // cfg["n_head"], max_position=cfg.get("n_positions", 1024),
                 norm_eps=cfg.get("layer_norm_epsilon", 1e-5), tie_embeddings=True,
                 bos_token_id=cfg.get("bos_token_id", 50256), eos_token_id=eos)
-        if mt not in ("llama", "mixtral", "mistral"):
-            raise ValueError(f"unsupported model_type {mt!r} (supported: llama, mistral, mixtral, gpt2)")
+        if mt in ("qwen2_moe", "qwen3_moe"):
+            raise ValueError(f"unsupported model_type {mt!r}: the MoE Qwen variants are not supported "
+                             "(supported: llama, mistral, mixtral, qwen2, qwen3, gpt2)")
+        if mt not in ("llama", "mixtral", "mistral", "qwen2", "qwen3"):
+            raise ValueError(f"unsupported model_type {mt!r} "
+                             "(supported: llama, mistral, mixtral, qwen2, qwen3, gpt2)")
+        if mt in ("qwen2", "qwen3"):
+            if cfg.get("use_sliding_window"):
+                raise ValueError(f"{mt}: use_sliding_window=true (sliding-window attention) is not supported")
+            other = sorted({t for t in (cfg.get("layer_types") or []) if t != "full_attention"})
+            if other:
+                raise ValueError(f"{mt}: layer_types {other} are not supported (only full_attention)")
         h = cfg["hidden_size"]
         nh = cfg["num_attention_heads"]
         return ModelConfig(
@@ -154,8 +177,15 @@ class ModelConfig:
             tie_embeddings=bool(cfg.get("tie_word_embeddings", False)),
             num_experts=cfg.get("num_local_experts", 0) if mt == "mixtral" else 0,
             experts_per_token=cfg.get("num_experts_per_tok", 0) if mt == "mixtral" else 0,
-            bos_token_id=cfg.get("bos_token_id", 1), eos_token_id=eos)
+            bos_token_id=cfg.get("bos_token_id", 1), eos_token_id=eos,
+            attn_bias=mt == "qwen2" or (mt == "qwen3" and bool(cfg.get("attention_bias", False))),
+            qk_norm=mt == "qwen3")
 
+
+# what models with ModelConfig.attn_bias / qk_norm (Qwen2, Qwen3) cannot run with yet
+QWEN_TP_REFUSAL = ("tensor parallelism (tp > 1) is not supported for models with a qkv bias or a q/k norm "
+                   "(Qwen2 / Qwen3): the bias shard is not built")
+QWEN_FP8_REFUSAL = ('quant="fp8" is not supported for models with a qkv bias or a q/k norm (Qwen2 / Qwen3)')
 
 _LLAMA3_ROPE = {"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0,
                 "high_freq_factor": 4.0, "original_max_position_embeddings": 8192}
@@ -181,6 +211,16 @@ PRESETS: Dict[str, ModelConfig] = {
         intermediate_size=3072, num_layers=12, num_heads=12, num_kv_heads=12, head_dim=64,
         max_position=1024, norm_eps=1e-5, tie_embeddings=True,
         bos_token_id=50256, eos_token_id=50256),
+    "qwen2.5-7b": ModelConfig(
+        name="qwen2.5-7b", arch="llama", vocab_size=152064, hidden_size=3584,
+        intermediate_size=18944, num_layers=28, num_heads=28, num_kv_heads=4, head_dim=128,
+        max_position=32768, rope_theta=1000000.0, norm_eps=1e-6, bos_token_id=151643, eos_token_id=151645,
+        attn_bias=True),
+    "qwen3-8b": ModelConfig(
+        name="qwen3-8b", arch="llama", vocab_size=151936, hidden_size=4096,
+        intermediate_size=12288, num_layers=36, num_heads=32, num_kv_heads=8, head_dim=128,
+        max_position=40960, rope_theta=1000000.0, norm_eps=1e-6, bos_token_id=151643, eos_token_id=151645,
+        qk_norm=True),
     # Tiny configs with the same structure, for CPU tests and GPU smoke runs.
     "tiny-llama": ModelConfig(
         name="tiny-llama", arch="llama", vocab_size=512, hidden_size=256,
@@ -191,6 +231,28 @@ PRESETS: Dict[str, ModelConfig] = {
         name="tiny-llama-d128", arch="llama", vocab_size=1024, hidden_size=512,
         intermediate_size=1024, num_layers=4, num_heads=4, num_kv_heads=1, head_dim=128,
         max_position=2048, rope_theta=500000.0, norm_eps=1e-5, bos_token_id=1, eos_token_id=2),
+    "tiny-qwen2": ModelConfig(
+        name="tiny-qwen2", arch="llama", vocab_size=512, hidden_size=256,
+        intermediate_size=512, num_layers=4, num_heads=4, num_kv_heads=2, head_dim=64,
+        max_position=1024, rope_theta=500000.0, norm_eps=1e-5, bos_token_id=1, eos_token_id=2,
+        attn_bias=True),
+    # q_size (512) != hidden_size (256), as in Qwen3-0.6B and Qwen3-4B
+    "tiny-qwen3": ModelConfig(
+        name="tiny-qwen3", arch="llama", vocab_size=512, hidden_size=256,
+        intermediate_size=512, num_layers=4, num_heads=8, num_kv_heads=2, head_dim=64,
+        max_position=1024, rope_theta=1000000.0, norm_eps=1e-6, bos_token_id=1, eos_token_id=2,
+        qk_norm=True),
+    "tiny-qwen3-d128": ModelConfig(
+        name="tiny-qwen3-d128", arch="llama", vocab_size=1024, hidden_size=512,
+        intermediate_size=1024, num_layers=4, num_heads=4, num_kv_heads=1, head_dim=128,
+        max_position=2048, rope_theta=500000.0, norm_eps=1e-5, bos_token_id=1, eos_token_id=2,
+        qk_norm=True, attn_bias=True),
+    # 7 q heads per kv head, as Qwen2.5-7B: a group the prefill attention kernels do not tile (models/stage.py pads it)
+    "tiny-qwen2-g7": ModelConfig(
+        name="tiny-qwen2-g7", arch="llama", vocab_size=512, hidden_size=256,
+        intermediate_size=512, num_layers=4, num_heads=7, num_kv_heads=1, head_dim=64,
+        max_position=1024, rope_theta=1000000.0, norm_eps=1e-6, bos_token_id=1, eos_token_id=2,
+        attn_bias=True),
     "tiny-mixtral": ModelConfig(
         name="tiny-mixtral", arch="mixtral", vocab_size=512, hidden_size=256,
         intermediate_size=384, num_layers=4, num_heads=4, num_kv_heads=2, head_dim=64,
@@ -312,6 +374,8 @@ class EngineConfig:
         cfg = get_model_config(self.model if self.shard_dir is None else self.shard_dir)
         if self.num_workers > cfg.num_layers:
             raise ValueError(f"{self.num_workers} stages > {cfg.num_layers} layers")
+        if self.quant == "fp8" and (cfg.attn_bias or cfg.qk_norm):
+            raise ValueError(QWEN_FP8_REFUSAL)
         if self.lora_modules:
             if not isinstance(self.lora_modules, dict):
                 raise ValueError("lora_modules must map adapter names to sources")
@@ -325,6 +389,10 @@ class EngineConfig:
             raise ValueError("prefix caching is not supported with tensor parallelism (tp > 1)")
         if tp > 1 and self.lora_modules:
             raise ValueError("LoRA adapters are not supported with tensor parallelism (tp > 1)")
+        if tp > 1:
+            cfg = self.model_config()
+            if cfg.attn_bias or cfg.qk_norm:
+                raise ValueError(QWEN_TP_REFUSAL)
 
     def model_config(self) -> ModelConfig:
         return get_model_config(self.shard_dir or self.model)

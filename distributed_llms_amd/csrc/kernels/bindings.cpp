@@ -15,6 +15,7 @@ PYBIND11_MODULE(_C_kernels, m) {
         py::arg("rows"), py::arg("hidden"), py::arg("eps"), py::arg("stream"));
   m.def("embedding", &dllm::embedding);
   m.def("rope_cache_append", &dllm::rope_cache_append);
+  m.def("qkv_prep", &dllm::qkv_prep);
   m.def("silu_mul", &dllm::silu_mul);
   m.def("argmax", &dllm::argmax);
   m.def("sample_rows", &dllm::sample_rows);

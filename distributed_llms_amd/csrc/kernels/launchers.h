@@ -18,6 +18,10 @@ void embedding(uintptr_t out, uintptr_t ids, uintptr_t table, int tokens, int hi
 void rope_cache_append(uintptr_t q_out, uintptr_t qkv, uintptr_t positions, uintptr_t cos_sin,
                        uintptr_t k_cache, uintptr_t v_cache, uintptr_t slots, int tokens, int hq, int hkv,
                        int d, int bs, int v_groups, uintptr_t stream);
+// qkv_prep.hip: Qwen2 qkv bias (bias [(Hq + 2 Hkv) D] or 0) and Qwen3 per-head RMSNorm over D on the q / k heads
+// (q_w / k_w [D] or 0), in place on the dense qkv [T, (Hq + 2 Hkv) D]; D is 64 or 128
+void qkv_prep(uintptr_t qkv, uintptr_t bias, uintptr_t q_w, uintptr_t k_w, int tokens, int hq, int hkv, int d,
+              float eps, uintptr_t stream);
 void silu_mul(uintptr_t out, uintptr_t gu, int tokens, int inter, uintptr_t stream);
 void add_inplace(uintptr_t a, uintptr_t b, long n, uintptr_t stream);
 void argmax(uintptr_t out, uintptr_t logits, int rows, int vocab, long row_stride, uintptr_t stream);

@@ -53,7 +53,7 @@ class DecodeGraphRunner:
         self.seq_lens.fill_(1)
         self.block_tables = self.dev_in[4 * mb:].view(mb, max_blocks)
         self.hidden = None if stage.is_first else torch.zeros(mb, stage.in_width, dtype=stage.dtype, device=dev)
-        self.ws = ops.decode_workspace(mb, cfg.num_heads, cfg.head_dim, dev)
+        self.ws = ops.decode_workspace(mb, max(cfg.num_heads, stage.hq), cfg.head_dim, dev)   # hq: padded GQA groups
         self.pinned = torch.empty(4 * mb + mb * max_blocks, dtype=torch.int32).pin_memory()
         self.pinned_np = self.pinned.numpy()
         self.graphs: Dict[Tuple[int, int, bool], Tuple[torch.cuda.CUDAGraph, torch.Tensor]] = {}

@@ -27,8 +27,8 @@ from .sampler import ids_message_len, max_ids_message_len, sample_step, unpack_i
 from .scheduler import Scheduler, Step
 from .logit_state import LogitState
 from ..models.lora import adapter_slots
-from .sequence import (SamplingParams, Sequence, request_seed, resolve_adapter, validate_logprobs,
-                       validate_processors)
+from .sequence import (SamplingParams, Sequence, fused_sampler_serves, request_seed, resolve_adapter,
+                       validate_logprobs, validate_processors, validate_sampling)
 
 log = logging.getLogger("dllm.engine")
 
@@ -120,6 +120,7 @@ class LLMEngine:
         if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
             # the processors rewrite whole logit rows; the tensor-parallel lanes hold vocabulary shards
             raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
+        validate_sampling(params, self.mcfg.vocab_size, fused_sampler_serves(self.stage.device, self.stage.dtype))
         slot = resolve_adapter(params.adapter, self.adapter_slots)
         seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id,
                        lora_slot=slot)

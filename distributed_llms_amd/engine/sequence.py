@@ -70,6 +70,29 @@ def validate_logprobs(value) -> Optional[int]:
     return value
 
 
+SAMPLE_MAX_VOCAB = 131072      # ops.SAMPLE_MAX_VOCAB: the row the fused sampler holds in registers
+
+
+def fused_sampler_serves(device, dtype, kernel_knobs=None) -> bool:
+    """Whether a stage on ``device`` with logits of ``dtype`` (a torch dtype or its EngineConfig name) draws
+    sampled rows with the fused HIP sampler (ops.sample_rows) and not the host reference."""
+    from .. import knobs
+    on = (kernel_knobs or {}).get("fused_sampler", knobs.K.fused_sampler)
+    return bool(on) and str(device).startswith("cuda") and str(dtype).replace("torch.", "") == "bfloat16"
+
+
+def validate_sampling(params, vocab_size: int, fused: bool) -> None:
+    """A request with temperature > 0 on a vocabulary the fused sampler cannot hold is refused when it is
+    admitted (ValueError): ops.sample_rows would raise inside a running step, after the step's KV was
+    written and with every other sequence of the batch in flight.  ``params``: a SamplingParams or a dict
+    of its fields; ``fused``: fused_sampler_serves() of the sampling stage."""
+    t = params.get("temperature", 0.0) if isinstance(params, dict) else params.temperature
+    if fused and vocab_size > SAMPLE_MAX_VOCAB and isinstance(t, (int, float)) and t > 0:
+        raise ValueError(f"temperature > 0 is not supported on this model: its vocabulary of {vocab_size} exceeds "
+                         f"the {SAMPLE_MAX_VOCAB} entries the fused GPU sampler holds; send temperature 0 (greedy) "
+                         f"or run with kernel_knobs fused_sampler=0 (host sampler)")
+
+
 MAX_LOGIT_BIAS = 300   # ops.reference.MAX_LOGIT_BIAS: bias entries of one request
 PROCESSOR_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "min_tokens")
 

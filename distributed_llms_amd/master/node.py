@@ -32,7 +32,8 @@ import time
 from typing import Any, Dict, List, Optional, Sequence
 
 from ..config import EngineConfig, ModelConfig, get_model_config
-from ..engine.sequence import resolve_adapter, validate_logprobs, validate_processors
+from ..engine.sequence import (fused_sampler_serves, resolve_adapter, validate_logprobs, validate_processors,
+                               validate_sampling)
 from ..models.lora import adapter_slots
 from ..network.protocol import MessageProtocol, pack_ids, unpack_ids, unpack_result
 from ..utils.metrics import RequestMetrics
@@ -538,6 +539,11 @@ class MasterNode:
             raise ValueError("logprobs are not available with stream")
         validate_processors(params, self.model_config.vocab_size if self.model_config else 1 << 31)     # normalises logit_bias to {int: float}
         resolve_adapter(params.get("adapter"), adapter_slots(self.config))     # an unknown name fails here, before dispatch
+        if self.model_config:      # by the configured device; a worker on another device checks again (worker/node.py)
+            from ..config import resolve_device
+            validate_sampling(params, self.model_config.vocab_size,
+                              fused_sampler_serves(resolve_device(self.config.device), self.config.dtype,
+                                                   self.config.kernel_knobs))
         with self._lock:
             # degraded with recovery on: hold the request with the parked in-flight ones (bounded)
             # until the stage is re-admitted (plan.md:430-436) -- checked under the

@@ -22,7 +22,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import knobs, ops
-from ..config import ModelConfig
+from ..config import QWEN_FP8_REFUSAL, QWEN_TP_REFUSAL, ModelConfig
 from ..ops import reference as ref
 from . import weights as W
 
@@ -85,7 +85,7 @@ class KVCache:
 # 3 / 4 the MLP over the first / second half of the intermediate columns.  A stage's unit range is
 # counted in units of ``unit_group`` per layer: 2 (halves: unit 0 = atoms 0-2, unit 1 = atoms 3-4)
 # or 5 (one unit per atom; parallel/planner.py).
-QKV_KEYS = {"attn_norm", "wqkv", "ln1_w", "ln1_b", "bqkv"}
+QKV_KEYS = {"attn_norm", "wqkv", "ln1_w", "ln1_b", "bqkv", "q_norm", "k_norm"}
 O_KEYS = {"wo", "bo"}
 ATTN_KEYS = QKV_KEYS | O_KEYS
 NATOM = 5
@@ -100,6 +100,17 @@ def unit_to_atom(u: int, group: int) -> int:
     return NATOM * (u // 2) + _HALF_ATOM[u % 2]
 
 
+GQA_GROUPS = (1, 2, 4, 8, 16)      # csrc/kernels/attention.hip dispatch_group
+
+
+def padded_group(g: int) -> int:
+    """The smallest GQA group the prefill attention kernels take that holds ``g`` q heads per kv head."""
+    for p in GQA_GROUPS:
+        if p >= g:
+            return p
+    raise ValueError(f"GQA group {g}: the attention kernels take at most {GQA_GROUPS[-1]} q heads per kv head")
+
+
 class ModelStage:
     """Layers ``[layer_start, layer_end)``, or -- finer -- half-layer *units* ``[u0, u1)``:
     unit 2l is the attention half of layer l (norm, qkv, RoPE + KV append, attention, o-proj),
@@ -109,16 +120,29 @@ class ModelStage:
     ``out_width``)."""
 
     def __init__(self, cfg: ModelConfig, layer_start: int, layer_end: int, device="cpu",
-                 dtype=torch.bfloat16, units: Optional[tuple] = None, tp=None, unit_group: int = 2):
+                 dtype=torch.bfloat16, units: Optional[tuple] = None, tp=None, unit_group: int = 2,
+                 pad_heads: Optional[bool] = None):
         """``tp``: a :class:`~distributed_llms_amd.parallel.tensor_parallel.TPGroup` -- this rank then
         holds its column / row / vocab shard of every layer (parallel/tensor_parallel.py).
         ``units``: [u0, u1) in units of ``unit_group`` per layer (2 halves or 5 sub-layer atoms)."""
         from ..parallel.tensor_parallel import TPGroup, check_divisible
         self.tp = tp if tp is not None else TPGroup(0, 1)
+        if self.tp.enabled and (cfg.attn_bias or cfg.qk_norm):
+            raise ValueError(QWEN_TP_REFUSAL)
         check_divisible(cfg, self.tp.size, self.tp.moe)
         # heads this rank computes (all of them without TP)
         self.hq = cfg.num_heads // self.tp.size
         self.hkv = cfg.num_kv_heads // self.tp.size
+        # q heads per kv head the stage runs with: the prefill attention kernels tile 16 / G query rows and take
+        # G = 1, 2, 4, 8, 16, so on the GPU any other group (Qwen2.5-7B: 28 / 4 = 7) is padded to the next of
+        # them with all-zero q heads -- zero wqkv rows and bias, zero wo columns (_pad_heads), which leaves
+        # every output what it was; ``pad_heads`` forces it on or off (tests)
+        self.group = self.group_real = self.hq // max(1, self.hkv)
+        if pad_heads is None:
+            pad_heads = torch.device(device).type == "cuda" and not self.tp.enabled
+        if pad_heads and cfg.arch != "gpt2":
+            self.group = padded_group(self.group_real)
+            self.hq = self.hkv * self.group
         self.q_size_local = self.hq * cfg.head_dim
         g = int(unit_group)
         if units is None:
@@ -137,6 +161,9 @@ class ModelStage:
                 raise ValueError("sub-layer cuts need a dense SwiGLU model")
             if self.tp.enabled:
                 raise ValueError("sub-layer cuts are not combined with tensor parallelism")
+            if self.group != self.group_real:
+                raise ValueError(f"sub-layer cuts are not combined with a padded GQA group "
+                                 f"({self.group_real} -> {self.group} q heads per kv head)")
         self.layer_start, self.layer_end = a0 // NATOM, (a1 + NATOM - 1) // NATOM
         self.is_first = a0 == 0
         self.is_last = a1 == NATOM * cfg.num_layers
@@ -206,6 +233,25 @@ class ModelStage:
             lw["w_gate_up"] = torch.cat([gu[c0:c1], gu[i + c0:i + c1]], 0).contiguous()
             lw["w_down"] = lw["w_down"][:, c0:c1].contiguous()
 
+    def _pad_heads(self):
+        """Zero q heads up to ``self.group`` per kv head (see __init__): rows of wqkv and bqkv, columns of wo."""
+        g, gp, hkv, d = self.group_real, self.group, self.hkv, self.cfg.head_dim
+        if gp == g:
+            return
+
+        def pad_q(q):          # [hkv * g * d, ...] -> [hkv * gp * d, ...]
+            q = q.view(hkv, g, d, *q.shape[1:])
+            z = q.new_zeros(hkv, gp - g, d, *q.shape[3:])
+            return torch.cat([q, z], 1).reshape(hkv * gp * d, *q.shape[3:])
+
+        nq = hkv * g * d
+        for lw in self.layers:
+            for k in ("wqkv", "bqkv"):
+                if k in lw:
+                    lw[k] = torch.cat([pad_q(lw[k][:nq]), lw[k][nq:]], 0).contiguous()
+            if "wo" in lw:
+                lw["wo"] = pad_q(lw["wo"].t().contiguous()).t().contiguous()
+
     def needs_embed(self) -> bool:
         return self.is_first or (self.is_last and self.cfg.tie_embeddings)
 
@@ -232,6 +278,7 @@ class ModelStage:
                 from ..parallel.tensor_parallel import shard_block
                 lw = shard_block(cfg, lw, self.tp.rank, self.tp.size, self.tp.moe)   # one full layer at a time
             self.layers.append(lw)
+        self._pad_heads()
         self._slice_mlp_halves()
         if self.needs_embed():
             self.embed = W.synth_embed(cfg, seed, self.dtype, self.device)
@@ -251,6 +298,7 @@ class ModelStage:
         conv = lambda t: t.to(device=self.device, dtype=self.dtype).contiguous()
         self.layers = [{k: conv(v) for k, v in W.hf_to_block(cfg, l, sd).items() if self._keep(l, k)}
                        for l in range(self.layer_start, self.layer_end)]
+        self._pad_heads()
         self._slice_mlp_halves()
         if self.needs_embed():
             names = W.hf_embed_names(cfg)
@@ -270,6 +318,8 @@ class ModelStage:
             return self
         if mode != "fp8":
             raise ValueError(f"unknown quantization {mode!r} (none, fp8)")
+        if self.cfg.attn_bias or self.cfg.qk_norm:
+            raise ValueError(QWEN_FP8_REFUSAL)
         from ..ops import quant
         quant.quantize_layers(self.layers)
         return self
@@ -278,6 +328,9 @@ class ModelStage:
         """The adapters of ``ecfg.lora_modules`` for this stage's layers (models/lora.py); refuses what
         cannot run with them (ValueError)."""
         from . import lora
+        if ecfg.lora_modules and self.group != self.group_real:
+            raise ValueError(f"LoRA adapters are not supported on a stage that pads its GQA group "
+                             f"({self.group_real} -> {self.group} q heads per kv head)")
         self.lora = lora.build_stage_lora(self, ecfg)
         return self
 
@@ -430,11 +483,17 @@ class ModelStage:
                     else:
                         x, residual = ops.fused_add_rms_norm(h, residual, lw["attn_norm"], eps, quant_out=q8)
                     h = None
+                    prep = cfg.attn_bias or cfg.qk_norm
                     if meta.lora is not None:
                         # adapter rows in the step: dense projection output, then the adapter deltas
                         qkv = self._lora(ops.linear(x, lw["wqkv"], defer=False), x, l, "wqkv", meta)
                     else:
-                        qkv = ops.linear(x, lw["wqkv"], defer=knobs.K.defer_qkv and self.has(l, 1))
+                        qkv = ops.linear(x, lw["wqkv"], defer=knobs.K.defer_qkv and self.has(l, 1) and not prep)
+                    if prep:
+                        # Qwen2 qkv bias / Qwen3 per-head q, k RMSNorm, in place on the dense projection
+                        # output: attention (or the next stage, at a cut) sees prepared qkv
+                        ops.qkv_prep_(qkv, lw.get("bqkv"), lw.get("q_norm"), lw.get("k_norm"), self.hq, self.hkv,
+                                      cfg.head_dim, eps)
                     if not self.has(l, 1):
                         out_aux = self._dense(qkv)
                         break
@@ -448,7 +507,9 @@ class ModelStage:
                     # defer: a split-K o-projection's reduce is fused into the MLP half's add + RMSNorm
                     # (TP: row-parallel partial sums, all-reduced over the group)
                     if meta.lora is not None:
-                        h = self._lora(ops.linear(a, lw["wo"], defer=False), a, l, "wo", meta)
+                        h = self._lora(ops.linear(a, lw["wo"], lw.get("bo"), defer=False), a, l, "wo", meta)
+                    elif "bo" in lw:      # a Qwen3 config with attention_bias
+                        h = ops.linear(a, lw["wo"], lw["bo"])
                     elif self.tp.enabled:
                         h = self.tp.all_reduce_(ops.linear(a, lw["wo"]))
                     else:

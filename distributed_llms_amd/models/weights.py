@@ -2,6 +2,8 @@
 
 Runtime layout (what the kernels consume) per transformer block:
   llama / mixtral: attn_norm [H], wqkv [(Hq+2Hkv)D, H] (q|k|v fused), wo [H, HqD], mlp_norm [H],
+                   Qwen2 (attn_bias): bqkv [(Hq+2Hkv)D]; Qwen3 (qk_norm): q_norm [D], k_norm [D]
+                   (+ bo [H] when a Qwen3 config sets attention_bias)
                    dense: w_gate_up [2I, H] (gate|up fused), w_down [H, I]
                    moe:   router [E, H], experts_gate_up [E, 2I, H], experts_down [E, H, I]
   gpt2:            ln1_w, ln1_b, wqkv [3H, H], bqkv, wo [H, H], bo, ln2_w, ln2_b,
@@ -30,6 +32,9 @@ HEAD = -2        # pseudo layer index for final norm / lm head
 
 
 def block_shapes(cfg: ModelConfig) -> Dict[str, Tuple[int, ...]]:
+    """The model's tensors (what checkpoints hold and ``param_count`` counts).  A GPU ModelStage whose GQA
+    group is none of 1, 2, 4, 8, 16 holds wqkv / bqkv / wo with zero q heads padded in (models/stage.py
+    _pad_heads): there those three are wider than the shapes here, by ``stage.hq`` against ``cfg.num_heads``."""
     h, i, d = cfg.hidden_size, cfg.intermediate_size, cfg.head_dim
     if cfg.arch == "gpt2":
         return {
@@ -37,6 +42,12 @@ def block_shapes(cfg: ModelConfig) -> Dict[str, Tuple[int, ...]]:
             "ln2_w": (h,), "ln2_b": (h,), "w_fc": (i, h), "b_fc": (i,), "w_proj": (h, i), "b_proj": (h,),
         }
     s = {"attn_norm": (h,), "wqkv": (cfg.qkv_size, h), "wo": (h, cfg.q_size), "mlp_norm": (h,)}
+    if cfg.attn_bias:
+        s["bqkv"] = (cfg.qkv_size,)
+    if cfg.qk_norm:
+        s.update({"q_norm": (d,), "k_norm": (d,)})
+        if cfg.attn_bias:              # Qwen3 with attention_bias: its o projection has a bias too
+            s["bo"] = (h,)
     if cfg.is_moe:
         e = cfg.num_experts
         s.update({"router": (e, h), "experts_gate_up": (e, 2 * i, h), "experts_down": (e, h, i)})
@@ -74,7 +85,12 @@ def tensor_seed(seed: int, layer: int, name: str) -> int:
 
 
 def synth_tensor(seed: int, layer: int, name: str, shape, dtype, device, std: float = 0.02) -> torch.Tensor:
-    """Deterministic N(0, std) (norm weights = 1, biases = 0) generated directly on ``device``."""
+    """Deterministic N(0, std) (norm weights = 1, biases = 0) generated directly on ``device``.
+    The per-head q / k norm weights are 1 + N(0, 0.1): a forward that skips them changes tokens."""
+    if name in ("q_norm", "k_norm"):
+        g = torch.Generator(device=device)
+        g.manual_seed(tensor_seed(seed, layer, name))
+        return (1.0 + 0.1 * torch.randn(shape, generator=g, device=device)).to(dtype)
     if _is_norm(name):
         return torch.ones(shape, dtype=dtype, device=device)
     if _is_bias(name) and name not in ("bqkv",):
@@ -103,6 +119,12 @@ def hf_block_names(cfg: ModelConfig, layer: int) -> List[str]:
     p = f"model.layers.{layer}."
     names = [p + "input_layernorm.weight", p + "self_attn.q_proj.weight", p + "self_attn.k_proj.weight",
              p + "self_attn.v_proj.weight", p + "self_attn.o_proj.weight", p + "post_attention_layernorm.weight"]
+    if cfg.attn_bias:
+        names += [p + f"self_attn.{n}_proj.bias" for n in ("q", "k", "v")]
+    if cfg.qk_norm:
+        names += [p + "self_attn.q_norm.weight", p + "self_attn.k_norm.weight"]
+        if cfg.attn_bias:
+            names.append(p + "self_attn.o_proj.bias")
     if cfg.is_moe:
         names.append(p + "block_sparse_moe.gate.weight")
         for e in range(cfg.num_experts):
@@ -129,6 +151,14 @@ def block_to_hf(cfg: ModelConfig, layer: int, w: Dict[str, torch.Tensor]) -> Dic
     out = {p + "input_layernorm.weight": w["attn_norm"], p + "self_attn.q_proj.weight": q.contiguous(),
            p + "self_attn.k_proj.weight": k.contiguous(), p + "self_attn.v_proj.weight": v.contiguous(),
            p + "self_attn.o_proj.weight": w["wo"], p + "post_attention_layernorm.weight": w["mlp_norm"]}
+    if cfg.attn_bias:
+        bq, bk, bv = torch.split(w["bqkv"], [cfg.q_size, cfg.kv_size, cfg.kv_size], 0)
+        out.update({p + "self_attn.q_proj.bias": bq.contiguous(), p + "self_attn.k_proj.bias": bk.contiguous(),
+                    p + "self_attn.v_proj.bias": bv.contiguous()})
+    if cfg.qk_norm:
+        out.update({p + "self_attn.q_norm.weight": w["q_norm"], p + "self_attn.k_norm.weight": w["k_norm"]})
+        if cfg.attn_bias:
+            out[p + "self_attn.o_proj.bias"] = w["bo"]
     i = cfg.intermediate_size
     if cfg.is_moe:
         out[p + "block_sparse_moe.gate.weight"] = w["router"]
@@ -164,6 +194,13 @@ def hf_to_block(cfg: ModelConfig, layer: int, sd: Dict[str, torch.Tensor]) -> Di
         "wo": sd[p + "self_attn.o_proj.weight"],
         "mlp_norm": sd[p + "post_attention_layernorm.weight"],
     }
+    if cfg.attn_bias:
+        out["bqkv"] = torch.cat([sd[p + f"self_attn.{n}_proj.bias"] for n in ("q", "k", "v")], 0)
+    if cfg.qk_norm:
+        out["q_norm"] = sd[p + "self_attn.q_norm.weight"]
+        out["k_norm"] = sd[p + "self_attn.k_norm.weight"]
+        if cfg.attn_bias:
+            out["bo"] = sd[p + "self_attn.o_proj.bias"]
     if cfg.is_moe and (p + "mlp.experts.gate_up_proj") in sd:
         # transformers>=5 in-memory layout: already fused [E, 2I, H] / [E, H, I]
         out["router"] = sd[p + "mlp.gate.weight"]

@@ -25,7 +25,7 @@ __all__ = [
     "gelu_tanh", "rope_cache_append", "paged_attention_decode", "paged_attention_prefill",
     "argmax", "add_", "moe_route", "moe_mlp", "decode_split_plan", "paged_attention_decode_rope",
     "paged_attention_prefill_rope", "sample_rows", "token_logprobs", "logit_state_update",
-    "apply_logit_processors", "logit_state_count", "prefill_split_plan", "prefill_split_eligible",
+    "apply_logit_processors", "logit_state_count", "prefill_split_plan", "prefill_split_eligible", "qkv_prep_",
 ]
 
 
@@ -122,6 +122,31 @@ def fused_add_rms_norm(x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor,
     _ext.kernels().rms_norm(y.data_ptr(), x.data_ptr(), residual.data_ptr(), w.data_ptr(), x.numel() // h, h,
                             float(eps), _stream())
     return y, residual
+
+
+def qkv_prep_(qkv: torch.Tensor, bias: Optional[torch.Tensor], q_w: Optional[torch.Tensor],
+              k_w: Optional[torch.Tensor], hq: int, hkv: int, d: int, eps: float) -> torch.Tensor:
+    """Qwen2 qkv bias / Qwen3 per-head q, k RMSNorm over ``d``, in place on the dense projection output
+    ``qkv`` [T, (hq + 2 hkv) d] before RoPE (contract: ops/reference.py qkv_prep).  ``bias``
+    [(hq + 2 hkv) d], ``q_w`` / ``k_w`` [d], each optional; head slots that none of them touches are
+    neither read nor written.  One launch, nothing allocated: graph-capturable."""
+    if qkv.dim() != 2 or qkv.shape[1] != (hq + 2 * hkv) * d:
+        raise ValueError(f"qkv_prep_: qkv must be [T, {(hq + 2 * hkv) * d}], got {tuple(qkv.shape)}")
+    for t, name, n in ((bias, "bias", (hq + 2 * hkv) * d), (q_w, "q_w", d), (k_w, "k_w", d)):
+        if t is not None and (t.shape != (n,) or t.device != qkv.device):
+            raise ValueError(f"qkv_prep_: {name} must be [{n}] on qkv's device")
+    if not _gpu(qkv):
+        return ref.qkv_prep(qkv, bias, q_w, k_w, hq, hkv, d, eps)
+    _ck(qkv, "qkv_prep_.qkv")
+    for t, name in ((bias, "bias"), (q_w, "q_w"), (k_w, "k_w")):
+        if t is not None:
+            _ck(t, "qkv_prep_." + name)
+    if d not in (64, 128):
+        raise ValueError(f"qkv_prep_: head_dim must be 64 or 128, got {d}")
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    _ext.kernels().qkv_prep(qkv.data_ptr(), ptr(bias), ptr(q_w), ptr(k_w), qkv.shape[0], hq, hkv, d, float(eps),
+                            _stream())
+    return qkv
 
 
 def layer_norm(x, w, b, eps):

@@ -35,6 +35,28 @@ def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     return (y * w.float()).to(x.dtype)
 
 
+def qkv_prep(qkv: torch.Tensor, bias: Optional[torch.Tensor], q_w: Optional[torch.Tensor],
+             k_w: Optional[torch.Tensor], hq: int, hkv: int, d: int, eps: float) -> torch.Tensor:
+    """Qwen2 qkv bias and Qwen3 per-head q / k RMSNorm, in place on the dense qkv [T, (hq + 2 hkv) d].
+
+    For token t and head slot s: r = f32(qkv[t, s]) + f32(bias[s]) (no bias: r = f32(qkv[t, s])), never
+    rounded in between.  q slots (s < hq) with ``q_w`` and k slots (hq <= s < hq + hkv) with ``k_w``
+    become dtype(r * rsqrt(mean_d(r^2) + eps) * f32(w)), one rounding as in :func:`rms_norm`; every
+    other slot dtype(r).  Slots that neither the bias nor a norm touches are not written."""
+    v = qkv.view(qkv.shape[0], hq + 2 * hkv, d)
+    b = None if bias is None else bias.float().view(hq + 2 * hkv, d)
+    for s0, s1, w in ((0, hq, q_w), (hq, hq + hkv, k_w), (hq + hkv, hq + 2 * hkv, None)):
+        if b is None and w is None:
+            continue
+        r = v[:, s0:s1].float()
+        if b is not None:
+            r = r + b[s0:s1]
+        if w is not None:
+            r = r * torch.rsqrt(r.pow(2).mean(-1, keepdim=True) + eps) * w.float()
+        v[:, s0:s1] = r.to(qkv.dtype)
+    return qkv
+
+
 def fused_add_rms_norm(x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor,
                        eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
     """residual <- x + residual ; returns (rms_norm(residual) * w, residual)."""

@@ -38,8 +38,8 @@ from ..engine.runner import StageRunner
 from ..engine.sampler import ids_message_len, sample_step, unpack_ids_message
 from ..engine.scheduler import Scheduler, Step
 from ..engine.logit_state import LogitState
-from ..engine.sequence import (SamplingParams, Sequence, request_seed, resolve_adapter, validate_logprobs,
-                               validate_processors)
+from ..engine.sequence import (SamplingParams, Sequence, fused_sampler_serves, request_seed, resolve_adapter,
+                               validate_logprobs, validate_processors, validate_sampling)
 from ..models.lora import adapter_slots
 from ..utils.tracing import get_tracer
 from .comm import STOP, PendingIds, Transport
@@ -143,6 +143,8 @@ class PipelineDriver:
             raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
         if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
             raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
+        # the last stage samples: stages of one pipeline share a device type and dtype
+        validate_sampling(params, self.mcfg.vocab_size, fused_sampler_serves(self.device, self.runner.stage.dtype))
         seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id,
                        lora_slot=resolve_adapter(params.adapter, self.adapter_slots))
         seq.seed = request_seed(seq.params, self._seed_rng)

@@ -552,7 +552,11 @@ class WorkerNode:
                 batch, self._pending = self._pending, []
             last_activity = time.time()
             for sock, task_id, ids, params, stream in batch:
-                seq = target.add_request(ids, params, request_id=task_id)
+                try:
+                    seq = target.add_request(ids, params, request_id=task_id)
+                except ValueError as e:     # refused at admission: this request fails, the loop goes on serving
+                    self.proto.send_message(sock, "ERROR", metadata={"error": str(e), "task_id": task_id})
+                    continue
                 owners[task_id] = sock
                 if stream:
                     streams[task_id] = [seq, 0]

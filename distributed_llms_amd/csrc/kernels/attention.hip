@@ -41,24 +41,61 @@ struct KVChunk {
   bf16x8 v[D / 16];
 };
 
-template <int D, bool NT = false>
+template <int D>
 __device__ __forceinline__ void load_chunk(KVChunk<D>& c, const bf16* __restrict__ kblk,
                                            const bf16* __restrict__ vblk, int lane) {
   const int r = lane & 15, g = lane >> 4;
-// NT: the decode wave reads each K/V line once per step (cold, HBM): nontemporal loads cut the
-// attention alone 41.4 -> 35.3 us at B=256 / ctx 192 (profiles/attn_fused_ablation.md); prefill
-// re-reads a sequence's K/V for every q tile and keeps the default policy
-#define DLLM_KVLD(p) (NT ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p)) \
-                         : *reinterpret_cast<const bf16x8*>(p))
+  // default cache policy: prefill re-reads a sequence's K/V for every q tile (the decode wave, which
+  // reads each line once per step, loads nontemporal: load_chunk_rows)
 #pragma unroll
   for (int ks = 0; ks < D / 32; ++ks) {
-    c.ka[ks] = DLLM_KVLD(kblk + r * D + ks * 32 + 8 * g);
-    c.kb[ks] = DLLM_KVLD(kblk + (16 + r) * D + ks * 32 + 8 * g);
+    c.ka[ks] = *reinterpret_cast<const bf16x8*>(kblk + r * D + ks * 32 + 8 * g);
+    c.kb[ks] = *reinterpret_cast<const bf16x8*>(kblk + (16 + r) * D + ks * 32 + 8 * g);
   }
 #pragma unroll
   for (int dt = 0; dt < D / 16; ++dt)
-    c.v[dt] = DLLM_KVLD(vblk + g * 8 * D + (dt * 16 + r) * 8);
-#undef DLLM_KVLD
+    c.v[dt] = *reinterpret_cast<const bf16x8*>(vblk + g * 8 * D + (dt * 16 + r) * 8);
+}
+
+// load_chunk for the decode wave, as buffer loads through three descriptors that END behind the rows
+// and groups to load: 16 ka rows, 16 kb rows and 4 V^T groups for every chunk but a split's last,
+// whose block is admissible only up to its first nadm keys (the rest is stale cache that
+// compute_chunk masks to -inf).  krow32 puts keys 8j..8j+3 in rows 4j.. of the ka tile and keys
+// 8j+4..8j+7 in rows 4j.. of the kb tile, so the admissible rows of each tile are a prefix of it
+// (na, nb rows) and the admissible V^T groups ([4][D][8]) a prefix of the block (ng): the range
+// check hands every lane beyond them zeros without a memory request.  The counts are scalars
+// picked per chunk, so nothing selects or branches per lane, every chunk issues the same
+// 2 * D/32 + D/16 loads, and the vmcnt the consumer waits for stays exact (a separate loader for
+// the last chunk behind a wave-uniform branch compiled to a block that drained vmcnt(0) first).
+// A masked score is -inf and its probability an exact 0 whatever finite bytes K / V held, so the
+// result is bit-identical to loading the stale rows.
+//   khead / vhead : the (block, kv head) tile's address, wave-uniform to the compiler as well
+//                   (a descriptor built from anything else is read back lane by lane in a
+//                   waterfall loop around each load)
+template <int D>
+__device__ __forceinline__ void load_chunk_rows(KVChunk<D>& c, const bf16* khead, const bf16* vhead, int na, int nb,
+                                                int ng, int lane) {
+  const auto ra = __builtin_amdgcn_make_buffer_rsrc((void*)khead, (short)0, na * D * 2, 0x00020000);
+  const auto rb = __builtin_amdgcn_make_buffer_rsrc((void*)(khead + 16 * D), (short)0, nb * D * 2, 0x00020000);
+  const auto rv = __builtin_amdgcn_make_buffer_rsrc((void*)vhead, (short)0, ng * 8 * D * 2, 0x00020000);
+  // The lane offsets are worked out HERE, behind an opaque copy of the lane id: computed from `lane`
+  // itself every `offset + fragment constant` is loop-invariant, hoisted out of the chunk loop and
+  // held across it in a register of its own (12 at D = 128, which spilled).  Kept in this block, the
+  // constants fold into the loads' immediate offsets.
+  int l = lane;
+  asm volatile("" : "+v"(l));
+  const int r = l & 15, g = l >> 4;
+  const int ok = (r * D + 8 * g) * 2, ov = (g * 8 * D + r * 8) * 2;
+  // aux 2: nontemporal.  The decode wave reads each K/V line once per step (cold, HBM): nontemporal
+  // loads cut the attention alone 41.4 -> 35.3 us at B=256 / ctx 192 (profiles/attn_fused_ablation.md)
+#pragma unroll
+  for (int ks = 0; ks < D / 32; ++ks) {
+    c.ka[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, ok + ks * 64, 0, 2));
+    c.kb[ks] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rb, ok + ks * 64, 0, 2));
+  }
+#pragma unroll
+  for (int dt = 0; dt < D / 16; ++dt)
+    c.v[dt] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rv, ov + dt * 256, 0, 2));
 }
 
 // Online-softmax update of the wave's 16 columns with one loaded chunk.
@@ -357,27 +394,36 @@ __global__ void __launch_bounds__(WPB * 64, 2) attn_decode_kernel(   // 2nd arg:
   const size_t kv_head_stride = (size_t)kBS * D;
   const size_t head_off = (size_t)kvh * kv_head_stride;
   const size_t blk_stride = (size_t)hkv * kv_head_stride;
+  // The split's last chunk holds nadm admissible cache keys: those up to kmax, less the fused
+  // kernel's new key ctx - 1, which comes from registers.  Below a full block, that chunk loads
+  // only the rows and V^T groups that hold them (load_chunk_rows).  FUSED: nadm < 32 only in the
+  // split that owns the new key, and its V^T group is loaded even at nadm % 8 == 0 (none of its keys
+  // admissible yet), since patch() writes the whole group back.
+  const int nadm = (FUSED ? min(kmax, ctx - 2) : kmax) + 1 - (c1 - 1) * kBS;
+  const int ctail = c1 - 1;
+  const int na_t = 4 * (nadm >> 3) + min(nadm & 7, 4), nb_t = 4 * (nadm >> 3) + max((nadm & 7) - 4, 0);
+  const int ng_t = (nadm + (FUSED ? 1 : 0) + 7) >> 3;
+  // (the wave's kv head is uniform, but derived from threadIdx it is not so to the compiler)
+  const int kvh_u = __builtin_amdgcn_readfirstlane(kvh);
+  auto load = [&](KVChunk<D>& c, int chunk, int blk) {
+    const size_t base = ((size_t)blk * hkv + kvh_u) * kv_head_stride;
+    const bool tail = chunk == ctail;
+    load_chunk_rows<D>(c, k_cache + base, v_cache + base, __builtin_amdgcn_readfirstlane(tail ? na_t : 16),
+                       __builtin_amdgcn_readfirstlane(tail ? nb_t : 16),
+                       __builtin_amdgcn_readfirstlane(tail ? ng_t : 4), lane);
+  };
   for (int cb = c0; cb < c1; cb += 64) {            // 64 chunks (2048 keys) of block ids per pass
     const int n = min(64, c1 - cb);
     const int my_blk = cb == c0 ? blk_first : (lane < n ? bt[cb + lane] : 0);
     KVChunk<D> cur, nxt;
-    {
-      const size_t base = (size_t)__builtin_amdgcn_readlane(my_blk, 0) * blk_stride + head_off;
-      load_chunk<D, true>(cur, k_cache + base, v_cache + base, lane);
-    }
+    load(cur, cb, __builtin_amdgcn_readlane(my_blk, 0));
     finish_rope();
     int j = 0;
     for (; j + 2 <= n; j += 2) {                    // ping-pong: cur <-> nxt
-      {
-        const size_t base = (size_t)__builtin_amdgcn_readlane(my_blk, j + 1) * blk_stride + head_off;
-        load_chunk<D, true>(nxt, k_cache + base, v_cache + base, lane);
-      }
+      load(nxt, cb + j + 1, __builtin_amdgcn_readlane(my_blk, j + 1));
       patch(cur, cb + j, (size_t)__builtin_amdgcn_readlane(my_blk, j) * blk_stride + head_off);
       compute_chunk<D>(st, qf, cur, (cb + j) * kBS, kmax, scale_log2, lane);
-      if (j + 2 < n) {
-        const size_t base = (size_t)__builtin_amdgcn_readlane(my_blk, j + 2) * blk_stride + head_off;
-        load_chunk<D, true>(cur, k_cache + base, v_cache + base, lane);
-      }
+      if (j + 2 < n) load(cur, cb + j + 2, __builtin_amdgcn_readlane(my_blk, j + 2));
       patch(nxt, cb + j + 1, (size_t)__builtin_amdgcn_readlane(my_blk, j + 1) * blk_stride + head_off);
       compute_chunk<D>(st, qf, nxt, (cb + j + 1) * kBS, kmax, scale_log2, lane);
     }

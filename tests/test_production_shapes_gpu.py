@@ -21,76 +21,17 @@ import os
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from distributed_llms_amd.config import EngineConfig, get_model_config
 from distributed_llms_amd.engine.batch import build_host_batch
 from distributed_llms_amd.engine.llm_engine import LLMEngine
 from distributed_llms_amd.engine.sequence import SamplingParams
 from distributed_llms_amd.models.stage import ModelStage
-from distributed_llms_amd.ops import reference as ref
+from model_reference import _bf, _ref_logits
 
 pytestmark = pytest.mark.gpu
 
 BATCH = 256
-
-
-def _rms(x, w, eps):
-    return x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps) * w
-
-
-def _bf(t):
-    return t.to(torch.bfloat16).float()
-
-
-def _ref_logits(stage: ModelStage, w32, toks: torch.Tensor, chunk: int = 32, rnd=None) -> torch.Tensor:
-    """fp32 forward of ``toks`` [B, T] (all positions, causal); last-position logits [B, V].
-    ``rnd``: applied to every op's output -- ``_bf`` gives the bf16-storage / fp32-compute forward
-    (what an exact bf16 kernel stack would produce): its distance from the fp32 one is the error
-    floor of bf16 activations."""
-    r = rnd or (lambda t: t)
-    cfg = stage.cfg
-    hq, hkv, d, eps = cfg.num_heads, cfg.num_kv_heads, cfg.head_dim, cfg.norm_eps
-    out, margin = [], []
-    for b0 in range(0, toks.shape[0], chunk):
-        t = toks[b0:b0 + chunk]
-        b, n = t.shape
-        pos = torch.arange(n, device=t.device).repeat(b)
-        x = w32["embed"][t]
-        gap = torch.full((b,), float("inf"), device=t.device)
-        for lw in w32["layers"]:
-            h = r(_rms(x, lw["attn_norm"], eps))
-            qkv = r(h @ lw["wqkv"].t()).view(b * n, hq + 2 * hkv, d)
-            q = r(ref.apply_rope(qkv[:, :hq], pos, stage.cos_sin)).view(b, n, hq, d).transpose(1, 2)
-            k = r(ref.apply_rope(qkv[:, hq:hq + hkv], pos, stage.cos_sin)).view(b, n, hkv, d).transpose(1, 2)
-            v = qkv[:, hq + hkv:].reshape(b, n, hkv, d).transpose(1, 2)
-            k = k.repeat_interleave(hq // hkv, dim=1)
-            v = v.repeat_interleave(hq // hkv, dim=1)
-            a = r(F.scaled_dot_product_attention(q, k, v, is_causal=True, scale=stage.scale))
-            x = r(x + a.transpose(1, 2).reshape(b, n, hq * d) @ lw["wo"].t())
-            h = r(_rms(x, lw["mlp_norm"], eps)).view(b * n, -1)
-            if cfg.is_moe:
-                probs = torch.softmax(h @ lw["router"].t(), dim=-1)
-                top = probs.view(b, n, -1)[:, -1].topk(cfg.experts_per_token + 1, dim=-1).values
-                gap = torch.minimum(gap, top[:, -2] - top[:, -1])    # routing margin, last position
-                tw, ids = torch.topk(probs, cfg.experts_per_token, dim=-1)
-                tw = tw / tw.sum(-1, keepdim=True)
-                y = torch.zeros_like(h)
-                for e in range(cfg.num_experts):
-                    tok, slot = (ids == e).nonzero(as_tuple=True)
-                    if tok.numel():
-                        gu = h[tok] @ lw["experts_gate_up"][e].t()
-                        i = gu.shape[-1] // 2
-                        ye = (F.silu(gu[:, :i]) * gu[:, i:]) @ lw["experts_down"][e].t()
-                        y.index_add_(0, tok, ye * tw[tok, slot].unsqueeze(1))
-            else:
-                gu = h @ lw["w_gate_up"].t()
-                i = gu.shape[-1] // 2
-                y = r(F.silu(gu[:, :i]) * gu[:, i:]) @ lw["w_down"].t()
-            x = r(x + y.view(b, n, -1))
-        out.append(r(_rms(x[:, -1], w32["final_norm"], eps)) @ w32["lm_head"].t())
-        margin.append(gap)
-    return torch.cat(out), torch.cat(margin)
 
 
 def _check(got: torch.Tensor, ref_out, what: str, max_rel: float, mean_rel: float):

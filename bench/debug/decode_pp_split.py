@@ -29,8 +29,8 @@ def main():
     ap.add_argument("--splits", type=int, nargs="+", default=[1, 2, 4, 8, 16])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--calls", type=int, default=8)
-    ap.add_argument("--extra", type=int, nargs="*", default=[],
-                    help="extra gemm_pp variant bits to try (added to schedule 2)")
+    ap.add_argument("--extra", type=int, nargs="*", default=[], choices=range(1, 8),
+                    help="extra gemm_pp variant bits to try beside PP_SCHED2 (gemm.PP_BN128 | PP_NT | PP_GROUPED)")
     a = ap.parse_args()
     torch.manual_seed(0)
     K_ = _ext.kernels()
@@ -50,7 +50,7 @@ def main():
                 if s > 1 and (ks // s < 2 or (n // 256) * s > 512):
                     continue
                 for extra in [0] + a.extra:
-                    var = 64 | extra
+                    var = gemm.PP_SCHED2 | extra
                     tag = f"pp{s}" + (f"v{extra}" if extra else "")
                     if s == 1:
                         fns[tag] = (lambda w, var=var: K_.gemm_pp(y.data_ptr(), x.data_ptr(), w.data_ptr(), wsp.data_ptr(),

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 import torch
 
-from distributed_llms_amd import knobs, ops
+from distributed_llms_amd import ops
 from distributed_llms_amd.ops import gemm
 
 SHAPES = {"qkv": (6144, 4096, False), "o": (4096, 4096, False), "gate_up": (28672, 4096, True),
@@ -53,14 +53,14 @@ def main():
             for spec in a.pp:
                 f = spec.split(":")
                 bn, sp, nt = int(f[0]), int(f[1]), len(f) > 2 and f[2] == "nt"
-                var = 64 | (1 if bn == 128 else 0) | (2 if nt else 0)
+                var = gemm.PP_SCHED2 | (gemm.PP_BN128 if bn == 128 else 0) | (gemm.PP_NT if nt else 0)
                 fns[f"pp{bn}s{sp}{'nt' if nt else ''}"] = (lambda sp, var: lambda x, w: gemm.linear_pp(
                     x, w, splits=sp, swiglu=sw, variant=var))(sp, var)
             for sp in a.sq:
                 fns[f"sq{sp}"] = (lambda sp: lambda x, w: gemm.linear_sq(x, w, splits=sp, swiglu=sw))(sp)
             for bm in ([] if a.no_wide else a.bms):
                 for s in a.splits:
-                    v = knobs.K.wide_variant_split if s > 1 else knobs.K.wide_variant
+                    v = gemm.WIDE_SPLIT_VARIANT if s > 1 else gemm.WIDE_VARIANT
                     fns[f"w{bm}s{s}"] = (lambda bm, s, v: lambda x, w: gemm.linear_wide(
                         x, w, splits=s, swiglu=sw, variant=v | (bm << 8)))(bm, s, v)
             ok = {}

@@ -1,5 +1,5 @@
 """Decode GEMM microbenchmark: the engine's hand-written wide-M MFMA kernel (gemm_wide.hip, plus
-gemm_sq.hip with --sq and extra variants) vs hipBLASLt (torch), cold (rotating > 768 MB of weight
+gemm_sq.hip with --sq) vs hipBLASLt (torch), cold (rotating > 768 MB of weight
 copies, in-engine-like) or --warm, each implementation graph-captured, interleaved in one process
 (CDNA guide rule 24).  Reports time, weight-streaming TB/s and TFLOP/s.
     python bench/gemm_bench.py [--m 64 256] [--shapes qkv_8b gate_up_8b]
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
 
-from distributed_llms_amd import knobs, ops
+from distributed_llms_amd import ops
 from distributed_llms_amd.ops import gemm
 
 SHAPES = {  # name: (N, K, swiglu)
@@ -44,10 +44,7 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=list(SHAPES))
     ap.add_argument("--warm", action="store_true", help="no cache flush between calls (in-engine-like)")
     ap.add_argument("--splits", type=int, default=0)
-    ap.add_argument("--variants", type=int, nargs="*", default=[0],
-                    help="extra gemm_wide variants timed beside the engine's choice")
     ap.add_argument("--sq", action="store_true", help="also time the 256 x 256-tile gemm_sq kernel")
-    ap.add_argument("--sq-alt", type=int, default=0, help="--sq: second gemm_sq variant timed (sq0)")
     a = ap.parse_args()
     return wide(a)
 
@@ -66,14 +63,9 @@ def wide(a):
             x = torch.randn(m, k, device="cuda").to(torch.bfloat16)
             # one HIP graph per implementation: `copies` back-to-back calls, each on its own weight
             # copy (launch overhead out of the measurement, like the engine's captured decode step)
-            split = (a.splits or gemm.wide_splits(m, n, k, sw)) > 1
-            wv = knobs.K.wide_variant_split if split else knobs.K.wide_variant     # the engine's choice
             impls = {
-                "wide": lambda w: gemm.linear_wide(x, w, splits=a.splits, swiglu=sw, variant=wv),
-                **{f"v{v}": (lambda w, v=v: gemm.linear_wide(x, w, splits=a.splits, swiglu=sw, variant=v))
-                   for v in a.variants},
-                **({"sq": lambda w: gemm.linear_sq(x, w, swiglu=sw, variant=4),
-                    "sq0": lambda w: gemm.linear_sq(x, w, swiglu=sw, variant=a.sq_alt)} if a.sq and n % 256 == 0 else {}),
+                "wide": lambda w: gemm.linear_wide(x, w, splits=a.splits, swiglu=sw),
+                **({"sq": lambda w: gemm.linear_sq(x, w, swiglu=sw)} if a.sq and n % 256 == 0 else {}),
                 "blas": (lambda w: ops.silu_mul(F.linear(x, w))) if sw else (lambda w: F.linear(x, w)),
             }
             reps = max(copies, 8)
@@ -100,8 +92,7 @@ def wide(a):
             byt, fl_ = n * k * 2, 2.0 * m * n * k
             print(f"{name:12s} {m:4d} {t['wide']*1e6:8.1f} {byt/t['wide']/1e12:6.2f} {fl_/t['wide']/1e12:6.0f} "
                   f"{t['blas']*1e6:8.1f} {t['blas']/t['wide']:8.2f} "
-                  + " ".join(f"v{v} {t[f'v{v}']*1e6:6.1f}" for v in a.variants)
-                  + (f" sq {t['sq']*1e6:6.1f} ({t['wide']/t['sq']:.2f}x) sq0 {t['sq0']*1e6:6.1f}" if "sq" in t else ""),
+                  + (f" sq {t['sq']*1e6:6.1f} ({t['wide']/t['sq']:.2f}x)" if "sq" in t else ""),
                   flush=True)
 
 

@@ -18,10 +18,9 @@ import torch
 
 from distributed_llms_amd.ops import gemm
 
-CASES = [  # name, M, N, K, swiglu, splits, variant (| 64: schedule 2, | 16 / 32: schedule-1 ablations)
-    ("gate_up dec S2", 256, 28672, 4096, True, 2, 64), ("gate_up dec", 256, 28672, 4096, True, 1, 1),
-    ("gate pf S2", 8192, 14336, 4096, False, 1, 68), ("gate pf", 8192, 14336, 4096, False, 1, 4),
-    ("gate pf S2 BN128", 8192, 14336, 4096, False, 1, 69),
+CASES = [  # name, M, N, K, swiglu, splits, variant (gemm.PP_* bits)
+    ("gate_up dec", 256, 28672, 4096, True, 2, 64), ("gate pf", 8192, 14336, 4096, False, 1, 68),
+    ("gate pf BN128", 8192, 14336, 4096, False, 1, 69),
 ]
 
 
@@ -49,10 +48,9 @@ def main():
         def run(var):
             return gemm.linear_pp(x, ws_[next(it) % copies], splits=s, swiglu=sw, variant=var)
         for _ in range(10):
-            run((v & 7) | 8 | (v & 112))
+            run(v | 8)                                  # the profile build (variant bit 3): output as usual
         torch.cuda.synchronize()
         bn = 128 if v & 1 else 256
-        # ablations time the diagnostic build itself (their output is garbage)
         grid = (n // bn) * (-(-m // 256)) * s
         full = gemm._workspace(dev)[-grid * 512:].view(grid * 4, 128).cpu()
         rec = full[:, :4]
@@ -63,14 +61,14 @@ def main():
         ideal = 2 * 8 * (bn // 32) * 16
         per = (tot / nt).tolist()
         frac = (bt / tot).tolist()
-        t_real = timed(lambda: run((v & 7) | (v & 64) | (8 | (v & 48) if v & 48 else 0)))
+        t_real = timed(lambda: run(v))
         wg_us = (rt_ns / 1e3).view(-1, 4).max(dim=1).values
         print(f"{name:12s} M={m:5d} N={n:5d} K={k:5d} S={s:2d} BN={bn} var={v}: kernel {t_real:7.1f} us "
               f"({2.0 * m * n * k / t_real / 1e6:5.0f} TF) | WG loop median {statistics.median(wg_us.tolist()):6.1f} us, "
               f"sum/256 {wg_us.sum().item() / 256:7.1f} us | clock {ghz:.2f} GHz | cycles/K-tile "
               f"{statistics.median(per):6.0f} (ideal {ideal}, {ideal / statistics.median(per) * 100:3.0f} %) | "
               f"barrier share {statistics.median(frac) * 100:4.1f} %"
-              + (f" (IB1 {statistics.median(b1) * 100:.1f} %, IB3 {statistics.median(b3) * 100:.1f} %)" if v & 64 else ""),
+              f" (IB1 {statistics.median(b1) * 100:.1f} %, IB3 {statistics.median(b3) * 100:.1f} %)",
               flush=True)
         del ws_, x
         torch.cuda.empty_cache()

@@ -1,5 +1,6 @@
-"""Prefill-sized bf16 GEMMs: hipBLASLt (torch, + silu_mul for gate|up) vs the wide kernel with the
-grouped row-tile order (gemm_wide variant bit 64, SwiGLU fused into its epilogue).
+"""Prefill-sized bf16 GEMMs: hipBLASLt (torch, + silu_mul for gate|up) vs the wide kernel (unsplit, SwiGLU
+fused into its epilogue).  The grouped row-tile order this bench once timed beside it is retired
+(profiles/prefill_gemm.md has its numbers; gemm_pf serves prefill M).
 
     python bench/prefill_gemm_bench.py [--m 8192 32768] [--out profiles/prefill_gemm.md]
 """
@@ -44,8 +45,7 @@ def main():
             x = torch.randn(m, k, device="cuda").to(torch.bfloat16)
             impls = {
                 "blas": (lambda: ops.silu_mul(F.linear(x, w))) if sw else (lambda: F.linear(x, w)),
-                "wide": lambda: gemm.linear_wide(x, w, splits=1, swiglu=sw, variant=4),
-                "wide_grp": lambda: gemm.linear_wide(x, w, splits=1, swiglu=sw, variant=4 | 64),
+                "wide": lambda: gemm.linear_wide(x, w, splits=1, swiglu=sw),
             }
             for f in impls.values():
                 f()
@@ -64,11 +64,9 @@ def main():
         torch.cuda.empty_cache()
     if a.out:
         with open(a.out, "w") as f:
-            f.write("| shape | M | hipBLASLt (+silu_mul) us | wide us | wide grouped us | grouped vs hipBLASLt |\n"
-                    "|---|---|---|---|---|---|\n")
+            f.write("| shape | M | hipBLASLt (+silu_mul) us | wide us | wide vs hipBLASLt |\n|---|---|---|---|---|\n")
             for name, m, t in rows:
-                f.write(f"| {name} | {m} | {t['blas']*1e6:.0f} | {t['wide']*1e6:.0f} | {t['wide_grp']*1e6:.0f} | "
-                        f"{t['blas']/t['wide_grp']:.2f}x |\n")
+                f.write(f"| {name} | {m} | {t['blas']*1e6:.0f} | {t['wide']*1e6:.0f} | {t['blas']/t['wide']:.2f}x |\n")
 
 
 if __name__ == "__main__":

@@ -165,13 +165,12 @@ __global__ void __launch_bounds__(256, 1) gemm_pp_kernel(const bf16* __restrict_
   constexpr int GA = BM * PBK * 2 / 1024 / NW, GB = BN * PBK * 2 / 1024 / NW;  // glds per wave per K-tile
   constexpr int G = GA + GB;
   constexpr bool NT = (VAR & 1) != 0, GROUPED = (VAR & 2) != 0;
-  constexpr bool PROF = (VAR & 4) != 0;                // diagnostic build: cycle stamps around B_t
-  // diagnostic ablations (wrong results, timing only): no LDS-DMA pieces / no fragment reads in the loop
-  constexpr bool NOLOAD = (VAR & 8) != 0, NOREAD = (VAR & 16) != 0;
+  constexpr bool PROF = (VAR & 4) != 0;                // schedule 2 diagnostic build: cycle stamps, correct output
   // schedule 2 (VAR 32): a K-tile's fragments are all read into registers early in its first K-half,
   // so its slot is re-staged from then on -- LDS-DMA pieces spread over ~60 % of the K-tile instead
   // of bunched into half of K-half 1 (see the loop)
   constexpr bool SCHED2 = (VAR & 32) != 0;
+  static_assert(!PROF || SCHED2, "the diagnostic build is schedule 2's");
   constexpr bool SWIGLU = MODE == 2;
   constexpr int OUTW = SWIGLU ? BN / 2 : BN;           // output tile width (elements)
   // schedule 2 + SwiGLU: the epilogue stages gate and up as bf16 (the image is the full BN wide)
@@ -382,7 +381,7 @@ __global__ void __launch_bounds__(256, 1) gemm_pp_kernel(const bf16* __restrict_
         else
           acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1[c], fa1[r], acc[r][c], 0, 0, 0);
         if constexpr (i % 2 == 1 && i / 2 < NR) {
-          if constexpr (!NOREAD) rd1(base1, std::integral_constant<int, i / 2>{});
+          rd1(base1, std::integral_constant<int, i / 2>{});
         }
         if constexpr (i == IB1) {
           if constexpr (PROF) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(sb0) :: "memory");
@@ -398,7 +397,7 @@ __global__ void __launch_bounds__(256, 1) gemm_pp_kernel(const bf16* __restrict_
           }
         }
         if constexpr (i > IB1 && (i - IB1 - 1) % GE == 0 && (i - IB1 - 1) / GE < G) {
-          if constexpr (!NOLOAD) piece(slot, t + NB, (i - IB1 - 1) / GE);
+          piece(slot, t + NB, (i - IB1 - 1) / GE);
         }
         if constexpr (i == IB3) {
           if constexpr (PROF) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(sb0) :: "memory");
@@ -414,7 +413,7 @@ __global__ void __launch_bounds__(256, 1) gemm_pp_kernel(const bf16* __restrict_
           }
         }
         if constexpr (i > IB3 && (i - IB3 - 1) % 2 == 0 && (i - IB3 - 1) / 2 < NR) {
-          if constexpr (!NOREAD) rd0(base0, std::integral_constant<int, (i - IB3 - 1) / 2>{});
+          rd0(base0, std::integral_constant<int, (i - IB3 - 1) / 2>{});
         }
         __builtin_amdgcn_sched_barrier(0);
       });
@@ -467,12 +466,6 @@ __global__ void __launch_bounds__(256, 1) gemm_pp_kernel(const bf16* __restrict_
     // landed for every wave (RAW), and only then are the next tile's fragments read and this
     // slot re-staged.
     int slot = 0;                                      // ring slot of K-tile t
-    [[maybe_unused]] unsigned long long st0 = 0, sbt = 0, sbt0 = 0, rt0 = 0;
-    if constexpr (PROF) {
-      rt0 = __builtin_amdgcn_s_memrealtime();
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st0) :: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-    }
     for (int t = 0; t < nt; ++t) {
       const uint32_t cur = lds_base + (uint32_t)(slot * SLOT * 2);
       const int nslot = slot == NB - 1 ? 0 : slot + 1;
@@ -486,10 +479,10 @@ __global__ void __launch_bounds__(256, 1) gemm_pp_kernel(const bf16* __restrict_
           acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0[c], fa0[r], acc[r][c], 0, 0, 0);
 #pragma unroll
           for (int a = 0; a < RT; ++a)
-            if (!NOREAD && SC::pos(0, 0, a) == i) fa1[a] = pp_frag_dyn(base + a_off + a * 16 * 128);
+            if (SC::pos(0, 0, a) == i) fa1[a] = pp_frag_dyn(base + a_off + a * 16 * 128);
 #pragma unroll
           for (int b = 0; b < CT; ++b)
-            if (!NOREAD && SC::pos(0, 1, b) == i) fb1[b] = pp_frag_dyn(base + b_off + b * 16 * 128);
+            if (SC::pos(0, 1, b) == i) fb1[b] = pp_frag_dyn(base + b_off + b * 16 * 128);
           __builtin_amdgcn_sched_barrier(0);
         });
       }
@@ -505,42 +498,23 @@ __global__ void __launch_bounds__(256, 1) gemm_pp_kernel(const bf16* __restrict_
           acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1[c], fa1[r], acc[r][c], 0, 0, 0);
           if constexpr (i == SC::EB - 1) {
             // B_t: every read of this slot done (WAR), K-tile t + 1 landed for every wave (RAW)
-            if constexpr (PROF)
-              asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(sbt0) :: "memory");
-            else
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             pp_wait_n<G>(NB - 2);
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
-            if constexpr (PROF) {
-              __builtin_amdgcn_sched_barrier(0);
-              unsigned long long s1;
-              asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(s1) :: "memory");
-              sbt += s1 - sbt0;
-              __builtin_amdgcn_sched_barrier(0);
-            }
           }
           if constexpr (i >= SC::EB - 1 && (i - SC::EB + 1) % GE == 0 && (i - SC::EB + 1) / GE < G)
-            if constexpr (!NOLOAD) piece(slot, t + NB, (i - SC::EB + 1) / GE);
+            piece(slot, t + NB, (i - SC::EB + 1) / GE);
 #pragma unroll
           for (int a = 0; a < RT; ++a)
-            if (!NOREAD && SC::pos(1, 0, a) == i) fa0[a] = pp_frag_dyn(base + a_off + a * 16 * 128);
+            if (SC::pos(1, 0, a) == i) fa0[a] = pp_frag_dyn(base + a_off + a * 16 * 128);
 #pragma unroll
           for (int b = 0; b < CT; ++b)
-            if (!NOREAD && SC::pos(1, 1, b) == i) fb0[b] = pp_frag_dyn(base + b_off + b * 16 * 128);
+            if (SC::pos(1, 1, b) == i) fb0[b] = pp_frag_dyn(base + b_off + b * 16 * 128);
           __builtin_amdgcn_sched_barrier(0);
         });
       }
       slot = nslot;
-    }
-    if constexpr (PROF) {   // per wave: loop cycles, cycles in B_t (counter waits + barrier), K-tiles, 100 MHz ticks
-      unsigned long long st1;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st1) :: "memory");
-      const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      const float vals[4] = {(float)(st1 - st0), (float)sbt, (float)nt, (float)(rt1 - rt0)};
-      float* rec = D + ((size_t)blockIdx.x * 4 + wv) * 128;
-      if (lane < 4) rec[lane] = vals[lane & 3];
     }
   }
   }
@@ -610,7 +584,7 @@ __global__ void __launch_bounds__(256, 1) gemm_pp_kernel(const bf16* __restrict_
       *reinterpret_cast<int4*>(C + (size_t)m * ldc + col0) = v;
     }
   }
-  if constexpr (PROF && SCHED2) {   // timeline of this wave (100 MHz ticks) + where it ran
+  if constexpr (PROF) {   // timeline of this wave (100 MHz ticks) + where it ran
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned long long rt_end = __builtin_amdgcn_s_memrealtime();
     unsigned hw, xcc;
@@ -642,10 +616,12 @@ int gemm_pp(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats,
   const bool nt = (variant & 2) != 0;
   const bool grp = (variant & 4) != 0 && S == 1 && mtiles > 1;
   // variant bit 6: schedule 2 (the K-tile's fragments read early, staging spread; weights
-  // nontemporal with bit 1 only in the natural tile order).  Bit 3: diagnostic build -- per-wave cycle stamps (loop, B_t waits) into the LAST
-  // grid x 512 floats of ws (after the slabs); output as usual.  With it (schedule 1 only), bit 4:
-  // no LDS-DMA pieces in the loop, bit 5: no fragment reads in the loop (ablations: wrong results,
-  // timing only)
+  // nontemporal with bit 1 only in the natural tile order).  Bit 3, with bit 6: its diagnostic build --
+  // per-wave cycle stamps and timeline into the LAST grid x 512 floats of ws (after the slabs); output
+  // as usual (bench/pp_timeline.py, bench/pp_stamps.py).  Schedule 1's diagnostic build and the
+  // no-load / no-read ablations (bits 4, 5) are retired (profiles/gemm_variants.md)
+  DLLM_HOST_CHECK((variant & ~(64 | 15)) == 0 && (!(variant & 8) || (variant & 64)),
+                  "gemm_pp variant retired: the ablation builds and schedule 1's profile build are gone");
   const bool sched2 = (variant & 64) != 0;
   const bool prof = (variant & 8) != 0;
   float* dbg = nullptr;
@@ -653,14 +629,12 @@ int gemm_pp(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats,
     DLLM_HOST_CHECK(ws != 0 && grid * 512 + (S > 1 ? (long)S * M * N : 0) <= ws_floats, "profile build: ws too small");
     dbg = (float*)ws + (ws_floats - grid * 512);
   }
-  // the kernel's VAR: bit 0 weights nt, bit 1 grouped order, bit 2 profile (+ 8 / 16: its ablations), bit 5 schedule 2
-  const int VAR = sched2 ? (prof ? (grp ? 38 : 36) : grp ? 34 : nt ? 33 : 32)
-                : prof   ? (grp ? 6 : (variant & 16) ? 12 : (variant & 32) ? 20 : 4)
-                         : (grp ? 2 : 0) + (nt ? 1 : 0);
+  // the kernel's VAR: bit 0 weights nt, bit 1 grouped order, bit 2 profile (schedule 2 only), bit 5 schedule 2
+  const int VAR = sched2 ? (prof ? (grp ? 38 : 36) : grp ? 34 : nt ? 33 : 32) : (grp ? 2 : 0) + (nt ? 1 : 0);
   // the kernel's MODE: 0 plain, 2 SwiGLU; 1 = a K split: natural column order slabs (a SwiGLU is applied by the reduce)
   dispatch_value<0, 1, 2>(S > 1 ? 1 : mode == 1 ? 2 : 0, "mode", [&](auto km) {
     dispatch_value<256, 128>(BN, "column tile", [&](auto bn) {
-      dispatch_value<0, 1, 2, 3, 4, 6, 12, 20, 32, 33, 34, 36, 38>(VAR, "variant", [&](auto var) {
+      dispatch_value<0, 1, 2, 3, 32, 33, 34, 36, 38>(VAR, "variant", [&](auto var) {
         hipLaunchKernelGGL((gemm_pp_kernel<decltype(bn)::value, decltype(km)::value, decltype(var)::value>),
                            dim3((unsigned)grid), dim3(256), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)c, (float*)ws, M,
                            N, K, sk.kts, S, dbg, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, 0);

@@ -16,8 +16,10 @@
 // v_mfma_f32_16x16x32_bf16 per wave):
 //  * global -> LDS by global_load_lds_dwordx4, 8 rows x 128 B per wave-instruction, bank swizzle
 //    chunk ^ ((row >> 1) & 7) on the per-lane SOURCE address and on the ds_read address (rule 21);
-//  * tile t + 1's eight LDS-DMA pieces per thread are issued between tile t's MFMAs; one
+//  * tile t + 1's eight LDS-DMA pieces per thread are issued right after the barrier, ahead of
+//    tile t's MFMAs (with two buffers, spreading them over the MFMAs lost 13 %: profiles/wide_gemm.md); one
 //    vmcnt(0) + raw s_barrier per K-tile; all LDS in one __shared__ array (trap 4a);
+//  * the weights are streamed nontemporally (read once) exactly where the grid has no K split;
 //  * XCD-aware bijective block remap (the K slices of one N tile run back-to-back on one XCD);
 //  * SwiGLU without a split: 16-row groups alternate gate / up rows so that a lane holds gate and up
 //    of one output column in neighbouring accumulators (as in gemm_wide.hip);
@@ -52,9 +54,7 @@ __device__ __forceinline__ int sq_b_row(int r, int n_t, int half) {
 }
 }  // namespace
 
-// VAR bit 0..1: weight cache policy (2 = nontemporal); bit 2 (EARLY): issue all of tile t + 1's
-// staging pieces right after the barrier instead of spreading them over tile t's MFMAs
-template <bool SPLIT, bool SWIGLU, int VAR>
+template <bool SPLIT, bool SWIGLU>
 __global__ void __launch_bounds__(512, 1) gemm_sq_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                                                          bf16* __restrict__ C, float* __restrict__ P, int M, int N,
                                                          int K, int kt_per_split, int nsplit) {
@@ -88,11 +88,7 @@ __global__ void __launch_bounds__(512, 1) gemm_sq_kernel(const bf16* __restrict_
     const int r = 8 * (wv * QBI + j) + (lane >> 3);
     offB[j] = (uint32_t)(sq_b_row<SWIGLU>(r, n_t, N / 2) * K + kt0 * QBK + qswz(r, lane & 7) * 8);
   }
-  // weights streamed nontemporally (read once) where the grid has no K split (VAR 2)
-  constexpr int BAUX = (VAR & 3) == 2 ? 2 : 0;
-  constexpr bool EARLY = (VAR & 4) != 0;
-  constexpr bool NOSTAGE = (VAR & 8) != 0;      // ablation (wrong results): no staging in the loop
-  constexpr bool NOPIN = (VAR & 16) != 0;       // ablation: no sched_barrier between substeps
+  constexpr int BAUX = SPLIT ? 0 : 2;           // weights nontemporal where the grid has no K split
   auto piece = [&](bf16* base, int ko, int p) {
     if (p < QAI)
       __builtin_amdgcn_global_load_lds((glb_vptr_q)(A + offA[p] + ko), (lds_vptr_q)(base + (wv * QAI + p) * 512), 16,
@@ -109,14 +105,12 @@ __global__ void __launch_bounds__(512, 1) gemm_sq_kernel(const bf16* __restrict_
     for (int c = 0; c < QCT; ++c) acc[a][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int fr = lane & 15, fq = lane >> 4;
-  // one K-tile of MFMAs from buffer `cur`; with STG the next tile's QG pieces go out in between
+  // one K-tile of MFMAs from buffer `cur`; with STG the next tile's QG pieces go out first
   auto ktile = [&](int cur, bf16* dst, int ko, auto stg) {
     constexpr bool STG = decltype(stg)::value;
     const bf16* sa = smem + cur * QBUF;
     const bf16* sb = sa + QAEL;
-    constexpr int NMF = 2 * QRT * QCT;        // 64 MFMAs per wave per K-tile
-    constexpr int EVERY = NMF / (QG + 1);     // one staging piece every 7 MFMAs
-    if constexpr (STG && EARLY && !NOSTAGE) {
+    if constexpr (STG) {
 #pragma unroll
       for (int p = 0; p < QG; ++p) piece(dst, ko, p);
     }
@@ -136,17 +130,12 @@ __global__ void __launch_bounds__(512, 1) gemm_sq_kernel(const bf16* __restrict_
 #pragma unroll
       for (int rt = 0; rt < QRT; ++rt)
 #pragma unroll
-        for (int ct = 0; ct < QCT; ++ct) {
+        for (int ct = 0; ct < QCT; ++ct)
           acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[rt], fb[ct], acc[rt][ct], 0, 0, 0);
-          if constexpr (STG && !EARLY && !NOSTAGE) {
-            const int i = (s * QRT + rt) * QCT + ct + 1;
-            if (i % EVERY == 0 && i / EVERY <= QG) piece(dst, ko, i / EVERY - 1);
-          }
-        }
       // keep the next substep's 12 fragment reads below this one's MFMAs: hoisting them would
       // need 48 more VGPRs than the 256 a 2-wave-per-SIMD workgroup has (128 go to accumulators);
       // the partner wave on the SIMD covers their latency
-      if constexpr (!NOPIN) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
     }
   };
 
@@ -212,23 +201,18 @@ int gemm_sq(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats,
   const long grid = (long)(N / QBN) * mtiles * S;
   DLLM_HOST_CHECK(grid >= 1 && grid < (1L << 31), "grid");
   splitk_check_ws(sk, ws, ws_floats, M, N);
-  const bool early = variant & 4;
-  // unsplit: VAR 2, or 6 (early); split: natural column order slabs (the SwiGLU, if any, is applied by the
-  // reduce), VAR 1, 5 (early), or the ablations 13 / 21 (A/B only)
-  const int V = S == 1 ? (early ? 6 : 2) : variant == 12 ? 13 : variant == 20 ? 21 : early ? 5 : 1;
-  dispatch_value<0, 1>(S > 1, "split", [&](auto sp) {
-    constexpr bool SPLIT = decltype(sp)::value != 0;
-    auto go = [&](auto sw, auto v) {
-      hipLaunchKernelGGL((gemm_sq_kernel<SPLIT, decltype(sw)::value != 0, decltype(v)::value>), dim3((unsigned)grid),
-                         dim3(512), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)c, (float*)ws, M, N, K, sk.kts, S);
-    };
-    if constexpr (SPLIT)
-      dispatch_value<1, 5, 13, 21>(V, "variant", [&](auto v) { go(std::false_type{}, v); });
-    else
-      dispatch_value<0, 1>(mode == 1, "swiglu", [&](auto sw) {
-        dispatch_value<2, 6>(V, "variant", [&](auto v) { go(sw, v); });
-      });
-  });
+  // the one variant word left, always 4 (its value is kept for the recorded route table,
+  // tests/golden/gemm_routes.json); the spread staging (0) and the ablation words are retired
+  DLLM_HOST_CHECK(variant == 4, "gemm_sq variant retired: only 4 remains");
+  // split: natural column order slabs (the SwiGLU, if any, is applied by the reduce)
+  if (S > 1)
+    hipLaunchKernelGGL((gemm_sq_kernel<true, false>), dim3((unsigned)grid), dim3(512), 0, s, (const bf16*)a,
+                       (const bf16*)b, (bf16*)c, (float*)ws, M, N, K, sk.kts, S);
+  else
+    dispatch_value<0, 1>(mode == 1, "swiglu", [&](auto sw) {
+      hipLaunchKernelGGL((gemm_sq_kernel<false, decltype(sw)::value != 0>), dim3((unsigned)grid), dim3(512), 0, s,
+                         (const bf16*)a, (const bf16*)b, (bf16*)c, (float*)ws, M, N, K, sk.kts, S);
+    });
   return splitk_finish(sk, c, ws, M, N, mode, stream);
 }
 

@@ -27,14 +27,19 @@
 //    back-to-back on one XCD;
 //  * the next tile's LDS-DMA pieces are issued between the MFMAs (pinned with
 //    sched_group_barrier): +9 % on the MLP up projection over issuing them after the barrier;
-//  * variant bit 32 (the engine default): fragment reads in inline asm with one lgkmcnt wait per
-//    MFMA row, substep 1's reads issued under substep 0's MFMAs (hipcc otherwise waits
-//    lgkmcnt(0) for all 16 reads before a K-tile's first MFMA): 1-2 % per GEMM, bit-exact.
-// Measured and dropped (profiles/wide_gemm.md): BK = 32 with 6 stages and a fragment software
-// pipeline (slower: twice the barriers), 4/5 stages at BM = 128, weights pre-tiled into
-// contiguous 16 KiB tiles (+0-3 %), setprio, other read/MFMA/VMEM orders.  Ablations at M = 256:
-// no LDS reads = same time, no barrier = same time, no staging loads = -21 % -- the loop is bound
-// by the load pipeline with a ~50 %-busy MFMA phase behind it.
+//  * the weights are streamed nontemporally exactly where the grid has no K split: -3..-5 % on the
+//    MLP up projection from cold caches; on split-K grids nt costs up to +25 % at M = 128;
+//  * ROW_WAITS (variant bit 5, the engine's unsplit default): fragment reads in inline asm with one
+//    lgkmcnt wait per MFMA row, substep 1's reads issued under substep 0's MFMAs (hipcc otherwise
+//    waits lgkmcnt(0) for all 16 reads before a K-tile's first MFMA): 1-2 % per GEMM, bit-exact.
+// Measured and dropped (profiles/wide_gemm.md, profiles/gemm_variants.md): BK = 32 with 6 stages and
+// a fragment software pipeline (slower: twice the barriers), 4/5 stages at BM = 128, weights
+// pre-tiled into contiguous 16 KiB tiles (+0-3 %), setprio, other read/MFMA/VMEM orders, both
+// operands nontemporal, an L2 prefetch of the weight tile, the grouped row-tile order for bf16
+// (gemm_pf serves prefill M).  Variant word 0 keeps the first form (staging pieces issued after the
+// barrier, weights never nontemporal) as the tests' second implementation.  Ablations at M = 256: no LDS reads =
+// same time, no barrier = same time, no staging loads = -21 % -- the loop is bound by the load
+// pipeline with a ~50 %-busy MFMA phase behind it.
 #include "common.h"
 #include "launch_host.h"
 #include "launchers.h"
@@ -74,7 +79,7 @@ __device__ __forceinline__ void wait_tiles(int younger) {
   }
 }
 
-// Fragment reads the compiler does not count (inline asm), for the SPLITRD K-tile: hipcc waits
+// Fragment reads the compiler does not count (inline asm), for the ROW_WAITS K-tile: hipcc waits
 // lgkmcnt(0) before the first MFMA of a K-tile whenever LDS-DMA shares the loop, exposing the
 // latency of all 16 fragment reads of every wave at once; here each MFMA row waits only for its
 // own fragments (`+v` on the wait statement orders the MFMAs after it, guide §5.7 item 1 (ii)).
@@ -184,33 +189,23 @@ __device__ __forceinline__ void wide_epilogue(const f32x4 (&acc)[BM / 64][4], bf
 // The K loop shared by the dense and the grouped (MoE) wide kernels: stages A/B tiles through
 // NBUF LDS buffers (LDS-DMA, counted vmcnt, raw barrier) and accumulates acc = A_tile B_tile^T
 // over `nt` 64-deep K-tiles.  srcA/srcB: this lane's staging source for K-tile 0.
-// VAR & 128 (PF): every staging slot also issues one 4-byte LDS-DMA per lane into a 256-byte
-// scratch (`pf_lds`) from `pfB`, a line of the weight tile PFD slots ahead: the weight lines are
-// then in the XCD's L2 when their staging pieces go out, so a tile waits for an L2 hit instead of
-// an HBM round trip.  One more vm op per slot (counted waits use G + 1); results are unchanged.
-constexpr int PFD = 2;
-template <int BM, int NBUF, int VAR, bool FP8 = false>
+// WEIGHTS_NT: the weight tile is staged nontemporally (read once); ROW_WAITS: bf16 fragment reads in
+// asm with per-row waits (ktile_sr below); INTERLEAVE false: the next tile's pieces go out after the
+// barrier, not between the MFMAs (variant word 0).
+template <int BM, int NBUF, bool WEIGHTS_NT, bool ROW_WAITS, bool FP8 = false, bool INTERLEAVE = true>
 __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&srcA)[BM / 64],
                                               const bf16* const (&srcB)[2], int nt, f32x4 (&acc)[BM / 64][4],
-                                              int wv, int lane, const bf16* pfB = nullptr, bf16* pf_lds = nullptr) {
+                                              int wv, int lane) {
   constexpr int AEL = BM * WBK, BEL = WBN * WBK, BUF = AEL + BEL;
-  constexpr bool PF = (VAR & 128) != 0;
-  constexpr int AI = BM / 64, BI = 2, G0 = AI + BI, G = PF ? G0 + 1 : G0, RT = BM / 64;
-  // the L2 prefetch of the weight tile staged PFD slots after this one (clamped: counts stay static)
-  auto prefetch = [&](int tile) {
-    if constexpr (PF)
-      __builtin_amdgcn_global_load_lds((glb_vptr_w)(pfB + min(tile, nt - 1) * WBK), (lds_vptr_w)pf_lds, 4, 0, 0);
-  };
+  constexpr int AI = BM / 64, BI = 2, G = AI + BI, RT = BM / 64;
   const int wm = wv >> 1, wn = wv & 1;
-  // cache policy of the staging loads (aux: 2 = nt): VAR 2 streams the weights nt, VAR 3 both operands
-  constexpr int BAUX = (VAR & 7) >= 2 ? 2 : 0, AAUX = (VAR & 7) == 3 ? 2 : 0;
+  constexpr int BAUX = WEIGHTS_NT ? 2 : 0;    // cache policy of the weight staging loads (aux 2 = nt)
   auto stage = [&](int buf, int t) {
     bf16* base = smem + buf * BUF;
     const int ko = t * WBK;
 #pragma unroll
     for (int j = 0; j < AI; ++j)
-      __builtin_amdgcn_global_load_lds((glb_vptr_w)(srcA[j] + ko), (lds_vptr_w)(base + (wv * AI + j) * 512), 16, 0,
-                                       AAUX);
+      __builtin_amdgcn_global_load_lds((glb_vptr_w)(srcA[j] + ko), (lds_vptr_w)(base + (wv * AI + j) * 512), 16, 0, 0);
 #pragma unroll
     for (int j = 0; j < BI; ++j)
       __builtin_amdgcn_global_load_lds((glb_vptr_w)(srcB[j] + ko), (lds_vptr_w)(base + AEL + (wv * BI + j) * 512), 16,
@@ -226,8 +221,7 @@ __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&sr
   // one glds piece: p < AI -> A rows, else B rows
   auto piece = [&](bf16* base, int ko, int p) {
     if (p < AI)
-      __builtin_amdgcn_global_load_lds((glb_vptr_w)(srcA[p] + ko), (lds_vptr_w)(base + (wv * AI + p) * 512), 16, 0,
-                                       AAUX);
+      __builtin_amdgcn_global_load_lds((glb_vptr_w)(srcA[p] + ko), (lds_vptr_w)(base + (wv * AI + p) * 512), 16, 0, 0);
     else
       __builtin_amdgcn_global_load_lds((glb_vptr_w)(srcB[p - AI] + ko),
                                        (lds_vptr_w)(base + AEL + (wv * BI + p - AI) * 512), 16, 0, BAUX);
@@ -254,7 +248,7 @@ __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&sr
       }
     }
     constexpr int NMF = 2 * RT * 4;
-    constexpr int EVERY = NMF / (G0 + 1);
+    constexpr int EVERY = NMF / (G + 1);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -264,22 +258,22 @@ __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&sr
           acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s][rt], fb[s][ct], acc[rt][ct], 0, 0, 0);
           if constexpr (STG) {
             const int i = (s * RT + rt) * 4 + ct + 1;
-            if (i % EVERY == 0 && i / EVERY <= G0) piece(dst, ko, i / EVERY - 1);
+            if (i % EVERY == 0 && i / EVERY <= G) piece(dst, ko, i / EVERY - 1);
           }
         }
     if constexpr (STG) {
-      // pin the interleave: 8 LDS reads of substep 0, then (EVERY MFMAs, 1 VMEM) x G0, rest
+      // pin the interleave: 8 LDS reads of substep 0, then (EVERY MFMAs, 1 VMEM) x G, rest
       __builtin_amdgcn_sched_group_barrier(0x100, 2 * (RT + 4), 0);
 #pragma unroll
-      for (int g = 0; g < G0; ++g) {
+      for (int g = 0; g < G; ++g) {
         __builtin_amdgcn_sched_group_barrier(0x008, EVERY, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, NMF - G0 * EVERY, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, NMF - G * EVERY, 0);
     }
   };
 
-  // SPLITRD (VAR & 32): the same K-tile with asm fragment reads and per-row lgkmcnt waits:
+  // ROW_WAITS: the same K-tile with asm fragment reads and per-row lgkmcnt waits:
   // substep 0's reads, its first MFMA row, substep 1's reads (overlapping substep 0's MFMAs),
   // then each row waits only for its own A fragment; the G staging pieces are spread over rows.
   // Per-lane LDS byte offsets: fragment (rt | ct) of substep s sits at base_s + (rt | ct) * 2 KiB.
@@ -314,8 +308,8 @@ __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&sr
       if constexpr (STG) {
         const int r = s * RT + rt;
 #pragma unroll
-        for (int p = 0; p < G0; ++p)
-          if ((p * ROWS) / G0 == r) piece(dst, ko, p);
+        for (int p = 0; p < G; ++p)
+          if ((p * ROWS) / G == r) piece(dst, ko, p);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -361,7 +355,7 @@ __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&sr
       fb[ct] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     }
     constexpr int NMF = RT * 4;
-    constexpr int EVERY = NMF / (G0 + 1) > 0 ? NMF / (G0 + 1) : 1;
+    constexpr int EVERY = NMF / (G + 1) > 0 ? NMF / (G + 1) : 1;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -369,28 +363,25 @@ __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&sr
         acc[rt][ct] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[rt], fb[ct], acc[rt][ct], 0, 0, 0, 127, 0, 127);
         if constexpr (STG) {
           const int i = rt * 4 + ct + 1;
-          if (i % EVERY == 0 && i / EVERY <= G0) piece(dst, ko, i / EVERY - 1);
+          if (i % EVERY == 0 && i / EVERY <= G) piece(dst, ko, i / EVERY - 1);
         }
       }
     if constexpr (STG) {
       __builtin_amdgcn_sched_group_barrier(0x100, 2 * (RT + 4), 0);
 #pragma unroll
-      for (int g = 0; g < G0; ++g) {
+      for (int g = 0; g < G; ++g) {
         __builtin_amdgcn_sched_group_barrier(0x008, EVERY, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, NMF - G0 * EVERY, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, NMF - G * EVERY, 0);
     }
   };
-  constexpr bool SPLITRD = (VAR & 32) != 0 && RT <= 4 && !FP8;
+  constexpr bool SPLITRD = ROW_WAITS && RT <= 4 && !FP8;
 
   if (nt > 0) {
 #pragma unroll
     for (int p = 0; p < NBUF - 1; ++p)
-      if (p < nt) {
-        prefetch(p + PFD);
-        stage(p, p);
-      }
+      if (p < nt) stage(p, p);
     int cur = 0;
     int t = 0;
     // steady state: tile t + NBUF - 1 exists, NBUF - 2 younger tiles stay in flight
@@ -398,7 +389,6 @@ __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&sr
       wait_tiles<G>(NBUF - 2);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      prefetch(t + NBUF - 1 + PFD);
       // buffer (t-1) % NBUF was last read in iteration t-1, which every wave finished before
       // this barrier: refill it with tile t + NBUF - 1
       const int nb = cur == 0 ? NBUF - 1 : cur - 1;
@@ -406,7 +396,7 @@ __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&sr
         ktile8(cur, smem + nb * BUF, (t + NBUF - 1) * WBK, std::true_type{});
       } else if constexpr (SPLITRD) {
         ktile_sr(cur, smem + nb * BUF, (t + NBUF - 1) * WBK, std::true_type{});
-      } else if constexpr ((VAR & 7) == 0) {
+      } else if constexpr (!INTERLEAVE) {
         stage(nb, t + NBUF - 1);
         ktile(cur, smem, 0, std::false_type{});
       } else {
@@ -425,26 +415,25 @@ __device__ __forceinline__ void wide_mainloop(bf16* smem, const bf16* const (&sr
       cur = cur == NBUF - 1 ? 0 : cur + 1;
     }
   }
-
 }
 
-template <int BM, bool SPLIT, bool SWIGLU, int NBUF, int VAR>
+// INTERLEAVE (every word but 0): staging pieces between the MFMAs, and the weights staged nontemporally
+// exactly when the grid has no K split (header).
+template <int BM, bool SPLIT, bool SWIGLU, int NBUF, bool ROW_WAITS, bool INTERLEAVE>
 __global__ void __launch_bounds__(512, 1) gemm_wide_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                                                            bf16* __restrict__ C, float* __restrict__ P, int M, int N,
                                                            int K, int kt_per_split, int nsplit) {
   constexpr int AEL = BM * WBK, BEL = WBN * WBK, BUF = AEL + BEL;   // bf16 elements
   constexpr int AI = BM / 64;                 // A glds instructions per thread per tile
   constexpr int BI = 2;                       // B glds instructions per thread per tile
-  constexpr int G = AI + BI;                  // glds per thread per tile (vmcnt unit)
   constexpr int RT = BM / 64;                 // 16-row fragments per wave in M
-  constexpr int PFL = (VAR & 128) ? 128 : 0;  // L2-prefetch scratch (bf16 elements), same LDS array
-  static_assert(NBUF >= 3 && (NBUF * BUF + PFL) * 2 <= 160 * 1024, "LDS");
-  __shared__ __attribute__((aligned(16))) bf16 smem[NBUF * BUF + PFL];
+  static_assert(NBUF >= 3 && NBUF * BUF * 2 <= 160 * 1024, "LDS");
+  __shared__ __attribute__((aligned(16))) bf16 smem[NBUF * BUF];
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wm = wv >> 1, wn = wv & 1;
   const int mtiles = (M + BM - 1) / BM;
-  const int ntiles = SWIGLU ? (N / 2) / 64 : N / WBN;
+  const int half = N / 2;                     // SwiGLU: the first up row of the fused weight
   const int total = gridDim.x;
   // bijective XCD remap: blocks b with b % 8 == x run on XCD x; give XCD x a contiguous run
   int b = blockIdx.x;
@@ -452,17 +441,11 @@ __global__ void __launch_bounds__(512, 1) gemm_wide_kernel(const bf16* __restric
     const int q = total >> 3, r = total & 7, x = b & 7;
     b = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
   }
-  int m_t = b % mtiles, rest = b / mtiles;
-  int split = rest % nsplit, n_t = rest / nsplit;
-  if constexpr ((VAR & 64) != 0) {          // prefill M, no K split (grouped_tile)
-    grouped_tile(b, mtiles, ntiles, m_t, n_t);
-    split = 0;
-  }
+  const int m_t = b % mtiles, rest = b / mtiles;
+  const int split = rest % nsplit, n_t = rest / nsplit;
   const int m0 = m_t * BM;
   const int kt0 = split * kt_per_split;
-  // ablations (timing only, wrong results): VAR & 16 skips the K loop (launch + epilogue cost),
-  // VAR & 8 skips the epilogue stores (kept behind a never-true runtime test so the MFMAs stay)
-  const int nt = (VAR & 16) ? 0 : max(0, min(K / WBK, kt0 + kt_per_split) - kt0);
+  const int nt = max(0, min(K / WBK, kt0 + kt_per_split) - kt0);
 
   // per-lane staging sources: instruction i covers tile rows 8i .. 8i+7, lane -> (row, chunk)
   const bf16* srcA[AI];
@@ -477,20 +460,18 @@ __global__ void __launch_bounds__(512, 1) gemm_wide_kernel(const bf16* __restric
   for (int j = 0; j < BI; ++j) {
     const int i = wv * BI + j;
     const int r = 8 * i + (lane >> 3);
-    srcB[j] = B + (size_t)wide_b_row<SWIGLU>(r, n_t, N / 2) * K + (size_t)kt0 * WBK + wswz(r, lane & 7) * 8;
+    srcB[j] = B + (size_t)wide_b_row<SWIGLU>(r, n_t, half) * K + (size_t)kt0 * WBK + wswz(r, lane & 7) * 8;
   }
-  // PF: lanes l and l + 16k of wave w touch weight row 16 w + (l & 15) of the tile: 128 lines per K-tile
-  const bf16* pfB = B + (size_t)wide_b_row<SWIGLU>(16 * wv + (lane & 15), n_t, N / 2) * K + (size_t)kt0 * WBK;
   f32x4 acc[RT][4];
-  wide_mainloop<BM, NBUF, VAR>(smem, srcA, srcB, nt, acc, wv, lane, pfB, smem + NBUF * BUF);
-  if (VAR & 8) return;
+  wide_mainloop<BM, NBUF, !SPLIT && INTERLEAVE, ROW_WAITS, false, INTERLEAVE>(smem, srcA, srcB, nt, acc, wv, lane);
   wide_epilogue<BM, SPLIT, SWIGLU>(acc, C, P, M, N, m0, n_t, split, wm, wn, lane);
 }
 
 // FP8 (W8A8) variant: A [M, K] and B [N, K] OCP e4m3 bytes, per-row scales sa [M] (dynamic,
 // per token: ops/quant) and sb [N] (per output channel, at load time).  Staging is the bf16 kernel's
 // byte for byte: a 128 x 128-byte K-tile is 128 K of fp8, addressed as 64 bf16-sized units.
-template <int BM, bool SPLIT, bool SWIGLU, int NBUF, int VAR>
+// WEIGHTS_NT: weights staged nontemporally; GROUPED: the grouped row-tile order (both: unsplit grids).
+template <int BM, bool SPLIT, bool SWIGLU, int NBUF, bool WEIGHTS_NT, bool GROUPED>
 __global__ void __launch_bounds__(512, 1) gemm_wide_fp8_kernel(const uint8_t* __restrict__ A8,
                                                                const uint8_t* __restrict__ B8, const float* __restrict__ sa,
                                                                const float* __restrict__ sb, bf16* __restrict__ C,
@@ -515,7 +496,7 @@ __global__ void __launch_bounds__(512, 1) gemm_wide_fp8_kernel(const uint8_t* __
   }
   int m_t = b % mtiles, rest = b / mtiles;
   int split = rest % nsplit, n_t = rest / nsplit;
-  if constexpr ((VAR & 64) != 0) {          // prefill M, no K split (column tiles: N / 128 both ways)
+  if constexpr (GROUPED) {                  // prefill M, no K split (column tiles: N / 128 both ways)
     grouped_tile(b, mtiles, N / WBN, m_t, n_t);
     split = 0;
   }
@@ -535,7 +516,7 @@ __global__ void __launch_bounds__(512, 1) gemm_wide_fp8_kernel(const uint8_t* __
     srcB[j] = B + (size_t)wide_b_row<SWIGLU>(r, n_t, N / 2) * KU + (size_t)kt0 * WBK + wswz(r, lane & 7) * 8;
   }
   f32x4 acc[RT][4];
-  wide_mainloop<BM, NBUF, VAR, true>(smem, srcA, srcB, nt, acc, wv, lane);
+  wide_mainloop<BM, NBUF, WEIGHTS_NT, false, true>(smem, srcA, srcB, nt, acc, wv, lane);
   wide_epilogue<BM, SPLIT, SWIGLU, true>(acc, C, P, M, N, m0, n_t, split, wm, wn, lane, sa, sb);
 }
 
@@ -548,7 +529,7 @@ __global__ void __launch_bounds__(512, 1) gemm_wide_fp8_kernel(const uint8_t* __
 // the decode regime of Mixtral at B >= 128 (32-128 rows per expert), where the weight-streaming
 // grouped kernel (moe.hip) runs its MFMAs at a fraction of the rate.
 // ---------------------------------------------------------------------------------------------
-template <int BM, bool SWIGLU, int VAR, bool FP8 = false, int NBUF = 3>
+template <int BM, bool SWIGLU, bool WEIGHTS_NT, bool FP8 = false, int NBUF = 3>
 __device__ __forceinline__ void moe_wide_rows(bf16* smem, bf16* __restrict__ Y, const bf16* __restrict__ X,
                                               const int* __restrict__ gather, const bf16* __restrict__ We, int cnt,
                                               int off, int N, int K, int n_t, int wv, int lane,
@@ -577,7 +558,7 @@ __device__ __forceinline__ void moe_wide_rows(bf16* smem, bf16* __restrict__ Y, 
       srcB[j] = We + (size_t)wide_b_row<SWIGLU>(r, n_t, N / 2) * KU + wswz(r, lane & 7) * 8;
     }
     f32x4 acc[RT][4];
-    wide_mainloop<BM, NBUF, VAR, FP8>(smem, srcA, srcB, KU / WBK, acc, wv, lane);
+    wide_mainloop<BM, NBUF, WEIGHTS_NT, false, FP8>(smem, srcA, srcB, KU / WBK, acc, wv, lane);
     wide_epilogue<BM, false, SWIGLU, FP8>(acc, Y + (size_t)(off + r0) * ldy, nullptr, rows, N, 0, n_t, 0, wm, wn,
                                           lane, FP8 ? sa + off + r0 : nullptr, sb);
     __syncthreads();   // the next chunk's prologue refills buffers other waves may still read
@@ -612,15 +593,15 @@ __global__ void __launch_bounds__(512, 1) moe_wide_kernel(bf16* __restrict__ Y, 
   const bf16* We = W + (size_t)e * N * (FP8 ? K / 2 : K);
   const float* sb = FP8 ? wscale + (size_t)e * N : nullptr;
   constexpr int NB64 = moe_nbuf<64, NBUF_SEL>(), NB128 = moe_nbuf<128, NBUF_SEL>();
-  // an expert's weight tile is read once when its rows fit one row tile: stream it nt (variant 2);
+  // an expert's weight tile is read once when its rows fit one row tile: stream it nt;
   // with several row chunks the re-reads should hit the caches (default policy)
   if (cnt <= 64) {
-    if (nt) moe_wide_rows<64, SWIGLU, 2, FP8, NB64>(smem, Y, X, gather, We, cnt, off, N, K, blockIdx.x, wv, lane, sa, sb);
-    else moe_wide_rows<64, SWIGLU, 1, FP8, NB64>(smem, Y, X, gather, We, cnt, off, N, K, blockIdx.x, wv, lane, sa, sb);
+    if (nt) moe_wide_rows<64, SWIGLU, true, FP8, NB64>(smem, Y, X, gather, We, cnt, off, N, K, blockIdx.x, wv, lane, sa, sb);
+    else moe_wide_rows<64, SWIGLU, false, FP8, NB64>(smem, Y, X, gather, We, cnt, off, N, K, blockIdx.x, wv, lane, sa, sb);
   } else if (cnt <= 128 && nt) {
-    moe_wide_rows<128, SWIGLU, 2, FP8, NB128>(smem, Y, X, gather, We, cnt, off, N, K, blockIdx.x, wv, lane, sa, sb);
+    moe_wide_rows<128, SWIGLU, true, FP8, NB128>(smem, Y, X, gather, We, cnt, off, N, K, blockIdx.x, wv, lane, sa, sb);
   } else {
-    moe_wide_rows<128, SWIGLU, 1, FP8, NB128>(smem, Y, X, gather, We, cnt, off, N, K, blockIdx.x, wv, lane, sa, sb);
+    moe_wide_rows<128, SWIGLU, false, FP8, NB128>(smem, Y, X, gather, We, cnt, off, N, K, blockIdx.x, wv, lane, sa, sb);
   }
 }
 
@@ -690,14 +671,13 @@ static int wide_row_tile(int M, int& variant) {
   return bm_force ? bm_force : wide_bm(M);
 }
 
-// f(BM, SPLIT, SWIGLU, V as integral constants) for the runtime values: the ladder of both wide launchers
-// (V = 65, the grouped row-tile order, is only asked for on unsplit grids)
-template <int... Vs, typename F>
-static void wide_dispatch(int BM, bool split, bool swiglu, int V, F&& f) {
+// f(BM, SPLIT, SWIGLU, FORM as integral constants) for the runtime values: the ladder of both wide launchers
+template <int... Forms, typename F>
+static void wide_dispatch(int BM, bool split, bool swiglu, int form, F&& f) {
   dispatch_value<64, 128, 192, 256>(BM, "row tile", [&](auto bm) {
     dispatch_value<0, 1>(split, "split", [&](auto sp) {
       dispatch_value<0, 1>(swiglu, "swiglu", [&](auto sw) {
-        dispatch_value<Vs...>(V, "variant", [&](auto v) { f(bm, sp, sw, v); });
+        dispatch_value<Forms...>(form, "variant", [&](auto fm) { f(bm, sp, sw, fm); });
       });
     });
   });
@@ -722,25 +702,16 @@ int gemm_wide(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_float
   DLLM_HOST_CHECK(grid >= 1 && grid < (1L << 31), "grid");
   splitk_check_ws(sk, ws, ws_floats, M, N);
 
-  // weights nt (variant 2) where the grid has no K split: -3..-5 % on the MLP up projection from
-  // cold caches; on the split-K grids nt costs up to +25 % at M = 128 (profiles/wide_gemm.md)
-  // (variant 4 = variant 1 everywhere, for A/B runs)
-  // variant | 32: per-row fragment waits (SPLITRD in wide_mainloop; the engine default);
-  // ablations (A/B timing only): variant | 8 = no epilogue stores, | 16 = no K loop
-  const int abl = variant & 56;
-  const bool grp = (variant & 64) != 0 && S == 1;   // grouped row-tile order (large M)
-  const bool pf = (variant & 128) != 0;            // L2 prefetch of the weight tile (wide_mainloop PF)
-  variant &= 7;
-  if (variant == 1 && S == 1) variant = grp ? 1 : 2;
-  else if (variant == 4) variant = 1;
-  // the kernel's VAR: policy 1 or 2 (weights nt) under an ablation / prefetch / fragment-wait bit, else the
-  // grouped order, else policy 0 .. 3
-  const int nt = variant == 2;
-  const int V = abl == 8 ? 9 + nt : abl == 16 ? 17 + nt : pf && abl == 32 ? 161 + nt : pf ? 129 + nt
-              : abl == 32 ? 33 + nt : grp ? 65 : variant == 0 || variant == 3 ? variant : 1 + nt;
-  wide_dispatch<0, 1, 2, 3, 9, 10, 17, 18, 33, 34, 65, 129, 130, 161, 162>(BM, S > 1, swiglu, V, [&](auto bm, auto sp, auto sw, auto v) {
+  // the variant word (its values are kept for the recorded route table, tests/golden/gemm_routes.json):
+  // 1 = staging pieces between the MFMAs, weights nt on unsplit grids; 1 | 32 = the same with per-row fragment
+  // waits (ROW_WAITS in wide_mainloop; the engine's unsplit default); 0 = pieces after the barrier, never nt.
+  // The other policies and the ablation, grouped-order and prefetch bits are retired (profiles/gemm_variants.md)
+  DLLM_HOST_CHECK(variant == 0 || variant == 1 || variant == 33,
+                  "gemm_wide variant retired: 0, 1 and 1 | 32 (+ a row-tile override) remain");
+  wide_dispatch<0, 1, 33>(BM, S > 1, swiglu, variant, [&](auto bm, auto sp, auto sw, auto v) {
     constexpr bool SPLIT = decltype(sp)::value != 0, SW = decltype(sw)::value != 0;
-    hipLaunchKernelGGL((gemm_wide_kernel<decltype(bm)::value, SPLIT, SW, 3, decltype(v)::value>), dim3((unsigned)grid),
+    constexpr int V = decltype(v)::value;
+    hipLaunchKernelGGL((gemm_wide_kernel<decltype(bm)::value, SPLIT, SW, 3, V == 33, V != 0>), dim3((unsigned)grid),
                        dim3(512), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)c, (float*)ws, M, N, K, sk.kts, S);
   });
   return splitk_finish(sk, c, ws, M, N, mode, stream);
@@ -763,13 +734,15 @@ int gemm_wide_fp8(uintptr_t c, uintptr_t a, uintptr_t a_scale, uintptr_t b, uint
   const long grid = (long)ntiles * mtiles * S;
   DLLM_HOST_CHECK(grid >= 1 && grid < (1L << 31), "grid");
   splitk_check_ws(sk, ws, ws_floats, M, N);
-  // weights nt where the grid has no K split (as the bf16 kernel's variant 1); variant | 64: grouped
+  // weights nt where the grid has no K split (as the bf16 kernel) unless the word is 4; variant | 64: grouped
   // row-tile order for large M (no K split)
   const bool nt = (variant & 7) != 4 && S == 1;
   const bool grp = (variant & 64) != 0 && S == 1 && !nt;
-  wide_dispatch<1, 2, 65>(BM, S > 1, swiglu, nt ? 2 : grp ? 65 : 1, [&](auto bm, auto sp, auto sw, auto v) {
+  // form 0: weights cached, natural order; 1: weights nt; 2: weights cached, grouped order
+  wide_dispatch<0, 1, 2>(BM, S > 1, swiglu, nt ? 1 : grp ? 2 : 0, [&](auto bm, auto sp, auto sw, auto fm) {
     constexpr bool SPLIT = decltype(sp)::value != 0, SW = decltype(sw)::value != 0;
-    hipLaunchKernelGGL((gemm_wide_fp8_kernel<decltype(bm)::value, SPLIT, SW, 3, decltype(v)::value>),
+    constexpr int FORM = decltype(fm)::value;
+    hipLaunchKernelGGL((gemm_wide_fp8_kernel<decltype(bm)::value, SPLIT, SW, 3, FORM == 1, FORM == 2>),
                        dim3((unsigned)grid), dim3(512), 0, s, (const uint8_t*)a, (const uint8_t*)b,
                        (const float*)a_scale, (const float*)b_scale, (bf16*)c, (float*)ws, M, N, K, sk.kts, S);
   });

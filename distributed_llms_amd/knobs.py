@@ -5,7 +5,7 @@ through :func:`update` -- called with ``EngineConfig.kernel_knobs`` when an engi
 rank is built (so the values a run used are part of its config and of the bench JSON line) --
 or, for experiments, from ONE environment variable read once at import::
 
-    DLLM_KNOBS="wide_variant=1,defer_qkv=1"        # or a JSON object
+    DLLM_KNOBS="wide_small_bm=0,defer_qkv=1"       # or a JSON object
 
 Nothing else in the package reads kernel switches from the environment.  The op layer reads
 ``knobs.K.<field>`` at call time, so an update applies to every launch after it (HIP graphs
@@ -31,10 +31,6 @@ class Knobs:
     # which decode-sized GEMMs gemm_wide serves: "auto" (the cutovers below), "all", "none", or a
     # comma list of roles gate_up / down / proj
     wide: str = "auto"
-    # gemm_wide variant for unsplit grids (33: LDS-DMA interleaved + asm fragment reads with one
-    # lgkmcnt per MFMA row) and for split-K grids (1); in-engine A/B 27,123 vs 27,014 / 26,896 tok/s
-    wide_variant: int = 33
-    wide_variant_split: int = 1
     wide_gate_up_max_m: int = 256     # SwiGLU-fused gate|up on gemm_wide up to this M (then split-K gemm_pp / gemm_pf)
     wide_down_max_m: int = 384        # MLP down (K >= 8192, K > N) up to this M (512: split gemm_pp 59 vs 66 us)
     wide_proj_max_m: int = 256        # qkv / LM head up to this M (o: wide_o_max_m; down: wide_down_max_m)
@@ -62,7 +58,6 @@ class Knobs:
     sq: str = "all"
     sq_min_m: int = 225
     sq_split: bool = False
-    sq_variant: int = 4
     # prefill-sized GEMMs (above the decode kernels' ranges) on the hand-written 256 x 256 kernels
     # instead of hipBLASLt, from this M (0 = hipBLASLt): the persistent schedule-2 kernel gemm_pf
     # (pp_persistent; else gemm_pp schedule 2).  At T = 32768 (profiles/round4_gemm_counters.md):

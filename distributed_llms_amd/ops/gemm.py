@@ -43,17 +43,24 @@ import torch.nn.functional as F
 from .. import _ext
 from .. import knobs
 
-# Variant words of the launchers: the bits the host sets (csrc/kernels documents the A/B-only rest).
+# Variant words of the launchers.  Their numeric values are those of the recorded route table
+# (tests/golden/gemm_routes.json); a launcher refuses a word whose kernel was retired (profiles/gemm_variants.md).
 # gemm_pp: 128-column tile (else 256), weights nontemporal, grouped row-tile order (large M, no K split), schedule 2
+# (every route sets it; schedule 1 stays as the tests' second implementation); bit 3 with PP_SCHED2: the profile build
+# of bench/pp_timeline.py
 PP_BN128, PP_NT, PP_GROUPED, PP_SCHED2 = 1, 2, 4, 64
 PP_PREFILL_VARIANT = PP_SCHED2 | PP_GROUPED           # medium M and prefill: 256-column tile
 PP_GATE_UP_VARIANT = PP_SCHED2 | PP_NT | PP_BN128     # decode gate|up (& ~PP_BN128: the 256-column form)
 PP_HEAD_VARIANT = PP_SCHED2 | PP_NT                   # decode LM head (weights read once per step)
 PP_DOWN_VARIANT = PP_SCHED2 | PP_NT | PP_BN128        # long-K decode down projection, split
-# gemm_wide: bits 0-2 = knobs.wide_variant(_split) (1: weights nontemporal on unsplit grids, 4: never), then
-# per-row fragment waits, grouped row-tile order, L2 prefetch of the weight tile; from bit 8 (gemm_wide_fp8
-# too) a row-tile override (64 / 128 / 192 / 256; 0 = wide_bm(M))
-WIDE_SPLITRD, WIDE_GROUPED, WIDE_PREFETCH, WIDE_ROW_TILE_SHIFT = 32, 64, 128, 8
+# gemm_wide: bit 0 is set in every routed word (staging pieces between the MFMAs, weights nontemporal exactly on
+# unsplit grids; word 0, pieces after the barrier, stays for the tests), WIDE_SPLITRD adds per-row
+# fragment waits (unsplit grids: 27,123 vs 27,014 / 26,896 tok/s in the engine); from bit 8 (gemm_wide_fp8 too) a
+# row-tile override (64 / 128 / 192 / 256; 0 = wide_bm(M))
+WIDE_SPLITRD, WIDE_ROW_TILE_SHIFT = 32, 8
+WIDE_VARIANT = 1 | WIDE_SPLITRD                # unsplit grids
+WIDE_SPLIT_VARIANT = 1                         # split-K grids
+SQ_VARIANT = 4                                 # gemm_sq's one word (staging pieces right after the barrier)
 FP8_NT, FP8_CACHED, FP8_GROUPED = 1, 4, 64     # gemm_wide_fp8: weights nontemporal on unsplit grids / never; grouped order
 PF_NT_STORES, PF_DYNAMIC = 8, 16               # gemm_pf: nontemporal output stores; per-XCD dynamic tile queues (DYN)
 
@@ -334,7 +341,7 @@ def wide_splits(m: int, n: int, k: int, swiglu: bool = False, target_wgs: int = 
 def _wide_route(m, n, k, swiglu, splits=0, variant=-1, comm_cus=None) -> GemmRoute:
     bm = wide_row_tile(m, n, k, swiglu)
     s = ws_splits(splits or wide_splits(m, n, k, swiglu, comm_cus=comm_cus, bm=bm), m, n)
-    v = (knobs.K.wide_variant_split if s > 1 else knobs.K.wide_variant) if variant < 0 else variant
+    v = (WIDE_SPLIT_VARIANT if s > 1 else WIDE_VARIANT) if variant < 0 else variant
     if bm != wide_bm(m):
         v |= bm << WIDE_ROW_TILE_SHIFT
     return GemmRoute("wide", s, v, swiglu)
@@ -401,8 +408,7 @@ def sq_splits(m: int, n: int, k: int, target_wgs: int = 256) -> int:
 
 
 def _sq_route(m, n, k, swiglu, splits=0, variant=-1) -> GemmRoute:
-    return GemmRoute("sq", ws_splits(splits or sq_splits(m, n, k), m, n),
-                     knobs.K.sq_variant if variant < 0 else variant, swiglu)
+    return GemmRoute("sq", ws_splits(splits or sq_splits(m, n, k), m, n), SQ_VARIANT if variant < 0 else variant, swiglu)
 
 
 def linear_sq(x: torch.Tensor, w: torch.Tensor, splits: int = 0, swiglu: bool = False, defer: bool = False,

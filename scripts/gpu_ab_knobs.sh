@@ -1,5 +1,5 @@
 # In-engine A/B of kernel-dispatch knobs (distributed_llms_amd/knobs.py):
-#   AB_RUNS="base: v1:wide_variant=1 noq:defer_qkv=1;defer_o=0" AB_ARGS="--batch 256" bash scripts/gpu_ab_knobs.sh
+#   AB_RUNS="base: bm:wide_small_bm=0 noq:defer_qkv=1;defer_o=0" AB_ARGS="--batch 256" bash scripts/gpu_ab_knobs.sh
 # each run: bench.py with DLLM_KNOBS set to the spec after the colon (';' separates knobs).
 set -o pipefail
 mkdir -p gpurun_out

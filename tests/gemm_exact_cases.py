@@ -199,8 +199,7 @@ WIDE_M = [1, 64, 65, 128, 129, 192, 193, 256, 300, 384, 385, 512, 640]
 WIDE_M_CASES = [(m, 256, 512, 8, s, 1) for m in WIDE_M for s in (1, 3)]
 WIDE_BM_CASES = [(m, 256, 512, 8, s, 1 | (bm << 8)) for bm in (64, 128, 192, 256) for m in (65, 300)
                  for s in (1, 2)]
-WIDE_VARIANT_CASES = [(129, 256, 1024, 4, s, v) for v in (0, 1, 3, 4, 1 | 32, 1 | 128, 33 | 128)
-                      for s in (1, 3)] + [(2100, 256, 128, 8, 1, 4 | 64)]
+WIDE_VARIANT_CASES = [(129, 256, 1024, 4, s, v) for v in (0, 1, 1 | 32) for s in (1, 3)] + [(2100, 256, 128, 8, 1, 1)]
 WIDE_SPLIT_CASES = [(m, n, k, r, s, 1) for m, n, k, r, s in [
     (129, 128, 64, 8, 1), (129, 128, 64, 8, 2),          # splits > K / 64: one slice runs
     (300, 1024, 128, 8, 2), (129, 128, 128, 8, 16),      # 16 asked, 2 run
@@ -237,9 +236,9 @@ NORM_CASES = [(65, 1024, 128, 8, 2), (65, 4096, 512, 8, 8), (65, 1024, 1024, 4, 
 GUARD_M = [1, 65, 129, 257, 300]
 GUARD_SHAPE = (256, 192, 8, 3)
 # part E: (m, inter, k)
-SWIGLU_WIDE = [(m, 192, 256) for m in WIDE_M] + [(300, i, 256) for i in (64, 128, 1024)] + [(129, 128, 4096)]
+SWIGLU_WIDE = [(m, 192, 256) for m in WIDE_M] + [(300, i, 256) for i in (64, 128, 1024)] + [(129, 128, 4096)] + \
+              [(2100, 128, 256)]                           # prefill M: 9 row tiles
 SWIGLU_SQ = [(129, 128, 256), (225, 1024, 256), (256, 128, 4096)]
-SWIGLU_WIDE_GROUPED = [(2100, 128, 256)]                  # variant 4 | 64, grouped row-tile order
 SWIGLU_PF = [(1, 128, 256), (255, 128, 256), (256, 1024, 256), (257, 1024, 256), (300, 128, 4096), (4100, 128, 256)]
 SWIGLU_PP = [(v, m, i, k) for v in (0, 4, 6, 64, 68) for m, i, k in [(77, 128, 256), (257, 1024, 256)]] + \
             [(v, m, i, k) for v in (1, 5, 65) for m, i, k in [(77, 64, 256), (257, 192, 256), (300, 1024, 256)]] + \

@@ -61,7 +61,7 @@ def test_selector_case(m, n, k):
     assert bool(gx.survives_slab(c.w).all())
 
 
-@pytest.mark.parametrize("m,inter,k", sorted(set(gx.SWIGLU_WIDE + gx.SWIGLU_WIDE_GROUPED + gx.SWIGLU_SQ +
+@pytest.mark.parametrize("m,inter,k", sorted(set(gx.SWIGLU_WIDE + gx.SWIGLU_SQ +
                                                  gx.SWIGLU_PF + [c[1:] for c in gx.SWIGLU_PP] +
                                                  [c[1:] for c in gx.SWIGLU_DISPATCH_CASES] +
                                                  [(257, 256, 128), (4100, 256, 128)])))

@@ -75,8 +75,11 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def launch(kern, x, w, splits=1, mode=0, variant=0, y=None, ws=None, ws_floats=None):
-    """One launch of gemm_{wide,sq,pp,pf} through the raw binding -> (y, S)."""
+def launch(kern, x, w, splits=1, mode=0, variant=None, y=None, ws=None, ws_floats=None):
+    """One launch of gemm_{wide,sq,pp,pf} through the raw binding -> (y, S).  ``variant`` None: the shipped word."""
+    if variant is None:
+        variant = {"wide": gemm.WIDE_SPLIT_VARIANT if splits > 1 else gemm.WIDE_VARIANT, "sq": gemm.SQ_VARIANT,
+                   "pp": gemm.PP_SCHED2, "pf": 0}[kern]
     m, k = x.shape
     n = w.shape[0]
     kk = _ext.kernels()
@@ -132,8 +135,7 @@ def test_wide_row_tiles_forced(cuda, m, n, k, r, splits, variant):
 
 @pytest.mark.parametrize("m,n,k,r,splits,variant", gx.WIDE_VARIANT_CASES)
 def test_wide_variants(cuda, m, n, k, r, splits, variant):
-    """Variants 0, 1 (2 when unsplit), 3, 4, fragment waits (32), L2 prefetch (128) and the grouped
-    row-tile order (64) at prefill M."""
+    """Words 0 and 1 (weights nontemporal when unsplit), per-row fragment waits (32), and word 1 at prefill M."""
     run_plain("wide", m, n, k, r, splits, variant)
 
 
@@ -144,7 +146,7 @@ def test_wide_k_and_splits(cuda, m, n, k, r, splits, variant):
     run_plain("wide", m, n, k, r, splits, variant)
 
 
-@pytest.mark.parametrize("variant", [0, 4])
+@pytest.mark.parametrize("variant", [4])
 @pytest.mark.parametrize("m,n,k,r,splits", gx.SQ_CASES)
 def test_sq(cuda, m, n, k, r, splits, variant):
     run_plain("sq", m, n, k, r, splits, variant)
@@ -462,14 +464,8 @@ def run_swiglu(kern, m, inter, k, splits, variant):
 @pytest.mark.parametrize("m,inter,k", gx.SWIGLU_WIDE)
 def test_wide_swiglu(cuda, m, inter, k, splits):
     """gemm_wide's fused epilogue (64-column gate / up tiles; I = 64, 128, 192, 1024) at every M edge
-    of part A, and 2 K slices into the SwiGLU reduce."""
+    of part A and at prefill M (9 row tiles), and 2 K slices into the SwiGLU reduce."""
     run_swiglu("wide", m, inter, k, splits, 33 if splits == 1 else 1)
-
-
-@pytest.mark.parametrize("m,inter,k", gx.SWIGLU_WIDE_GROUPED)
-def test_wide_swiglu_grouped_tile_order(cuda, m, inter, k):
-    """The SwiGLU epilogue under the grouped row-tile order (variant 4 | 64) at prefill M."""
-    run_swiglu("wide", m, inter, k, 1, 4 | 64)
 
 
 @pytest.mark.parametrize("splits", [1, 2])

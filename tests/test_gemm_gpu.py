@@ -126,37 +126,6 @@ def test_wide_split_fragment_waits_bit_exact(cuda, m, n, k, splits, swiglu):
     assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("m,n,k,splits,swiglu", [(256, 28672, 4096, 1, True), (256, 4096, 14336, 8, False),
-                                                (256, 6144, 4096, 5, False), (192, 4096, 4096, 4, False),
-                                                (128, 2048, 1024, 2, False), (40, 1024, 512, 1, False),
-                                                (256, 2048, 192, 3, False), (64, 2048, 128, 2, True)])
-def test_wide_l2_prefetch_bit_exact(cuda, m, n, k, splits, swiglu):
-    """Variant bit 128 (one extra LDS-DMA per staging slot pulls a weight line PFD slots ahead into
-    L2; counted waits move to G + 1) only changes timing: bit-identical to the same variant without
-    it, for the unsplit SwiGLU grid (33), split-K grids (1), short K (fewer tiles than the prefetch
-    distance) and the 64-row tile."""
-    x, w = _bf(m, k), _bf(n, k, scale=0.05)
-    for v in (1, 33):
-        a = gemm.linear_wide(x, w, splits=splits, swiglu=swiglu, variant=v)
-        b = gemm.linear_wide(x, w, splits=splits, swiglu=swiglu, variant=v | 128)
-        assert torch.equal(a, b), v
-
-
-@pytest.mark.parametrize("m,n,k,swiglu", [(4500, 1024, 512, False), (5000, 2048, 256, True), (2048, 256, 128, False)])
-def test_wide_grouped_tile_order_bit_exact(cuda, m, n, k, swiglu):
-    """Variant bit 64 (grouped row-tile order for prefill M) only reorders the workgroups: every
-    tile runs the same MFMAs, so outputs are bit-identical to the plain order."""
-    x, w = _bf(m, k), _bf(n, k, scale=0.05)
-    a = gemm.linear_wide(x, w, splits=1, swiglu=swiglu, variant=4)
-    b = gemm.linear_wide(x, w, splits=1, swiglu=swiglu, variant=4 | 64)
-    assert torch.equal(a, b)
-    ref = x.float() @ w.float().t()
-    if swiglu:
-        g, u = ref.chunk(2, -1)
-        ref = torch.nn.functional.silu(g) * u
-    torch.testing.assert_close(b.float(), ref, rtol=2e-2, atol=2e-2)
-
-
 def test_splitk_slabs_keep_output_precision(cuda):
     """Split-K slabs are stored as f16 x 2^-6 (csrc/kernels/common.h, DLLM_PART_TYPE 2): the split
     result must stay within one bf16 ulp of the exact product (plus half an ulp of the output's typical
@@ -406,7 +375,8 @@ def test_long_k_down_on_split_gemm_pp(cuda, m):
 def test_launcher_host_checks(cuda, kern):
     """Every precondition the split-K launchers check on the host raises instead of launching: K or N off the
     tile, splits = 0, an unknown mode, mode 2 without a K split, a workspace declared too small, and (the two
-    wide launchers, which have one) a row-tile override of 96.  Every buffer is real and sized for the next
+    wide launchers, which have one) a row-tile override of 96; and a variant word whose kernel was retired is
+    refused, never mapped onto a surviving kernel.  Every buffer is real and sized for the next
     valid shape up (M = 65, N = 512, K = 256, two slabs), so a check that went missing would launch inside
     memory the test owns; only the declared workspace size is short."""
     from distributed_llms_amd import _ext
@@ -419,7 +389,10 @@ def test_launcher_host_checks(cuda, kern):
     fp8 = kern == "gemm_wide_fp8"
     kt = 128 if fp8 else 64
 
-    def launch(n=n, k=2 * kt, ws_floats=ws.numel(), splits=1, mode=0, variant=0):
+    shipped = {"gemm_wide": gemm.WIDE_VARIANT, "gemm_wide_fp8": gemm.FP8_NT, "gemm_pp": gemm.PP_SCHED2,
+               "gemm_sq": gemm.SQ_VARIANT}[kern]
+
+    def launch(n=n, k=2 * kt, ws_floats=ws.numel(), splits=1, mode=0, variant=shipped):
         ptrs = (x.data_ptr(), sa.data_ptr(), w.data_ptr(), sb.data_ptr()) if fp8 else (x.data_ptr(), w.data_ptr())
         return fn(y.data_ptr(), *ptrs, ws.data_ptr(), ws_floats, m, n, k, splits, mode, variant, stream)
 
@@ -429,8 +402,12 @@ def test_launcher_host_checks(cuda, kern):
     if kern in ("gemm_wide", "gemm_wide_fp8"):
         bad.append(dict(variant=1 | 96 << gemm.WIDE_ROW_TILE_SHIFT))
     if kern == "gemm_pp":
-        bad.append(dict(n=n + 64, variant=gemm.PP_BN128))                       # its 128-column tile
+        bad.append(dict(n=n + 64, variant=gemm.PP_SCHED2 | gemm.PP_BN128))      # its 128-column tile
     for kw in bad:
         with pytest.raises(RuntimeError, match="dllm kernel precondition"):
             launch(**kw)
+    retired = {"gemm_wide": [3, 4, 1 | 8, 1 | 128], "gemm_pp": [8, 64 | 16], "gemm_sq": [0, 12]}.get(kern, [])
+    for v in retired:
+        with pytest.raises(RuntimeError, match="dllm kernel precondition.*retired"):
+            launch(variant=v)
     torch.cuda.synchronize()

@@ -91,8 +91,8 @@ def test_sq_only_on_unsplit_grids():
     knobs.update(sq_split=True)
     assert gemm.use_sq(256, 4096, 14336)
     assert gemm.sq_splits(256, 4096, 14336) == 16 and gemm.sq_splits(256, 6144, 4096) == 10
-    assert gemm.route(256, 4096, 14336) == gemm.GemmRoute("sq", 16, knobs.K.sq_variant)
-    assert gemm.route(256, 6144, 4096) == gemm.GemmRoute("sq", 10, knobs.K.sq_variant)
+    assert gemm.route(256, 4096, 14336) == gemm.GemmRoute("sq", 16, gemm.SQ_VARIANT)
+    assert gemm.route(256, 6144, 4096) == gemm.GemmRoute("sq", 10, gemm.SQ_VARIANT)
 
 
 def test_knobs_move_the_cutovers_and_reject_unknown_names():
@@ -249,7 +249,7 @@ def test_lm_head_leaves_gemm_pp_while_comm_cus_are_reserved():
     finally:
         gemm.release_cus_for_comm()
     assert [r.kernel for r in routes] == ["pp", "sq"]
-    assert routes[1] == gemm.route(256, 128256, 4096, comm_cus=16) == gemm.GemmRoute("sq", 1, knobs.K.sq_variant)
+    assert routes[1] == gemm.route(256, 128256, 4096, comm_cus=16) == gemm.GemmRoute("sq", 1, gemm.SQ_VARIANT)
 
 
 def test_rope_in_kernel_gated_on_block_table_width():

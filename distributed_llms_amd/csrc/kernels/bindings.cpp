@@ -43,6 +43,8 @@ PYBIND11_MODULE(_C_kernels, m) {
   m.def("gemm_pp_moe", &dllm::gemm_pp_moe);
   m.def("gemm_pp", &dllm::gemm_pp);
   m.def("gemm_pf", &dllm::gemm_pf);
+  m.def("lm_head_logprobs", &dllm::lm_head_logprobs);
+  m.attr("LM_HEAD_WAVES") = dllm::kLmHeadWaves;
   m.def("moe_combine", &dllm::moe_combine);
   m.def("moe_wide_gemm", &dllm::moe_wide_gemm);
   m.def("moe_router_route", &dllm::moe_router_route);

@@ -27,31 +27,17 @@
 //  * SwiGLU without a weight permutation: the B tile's 16-row groups alternate gate / up rows of
 //    the fused [2I, K] weight, so gate and up of an output column meet in one lane.
 #include "common.h"
+#include "gemm_pp_loop.h"
 #include "launch_host.h"
 #include "launchers.h"
 
 #include <atomic>
 #include <mutex>
-#include <type_traits>
 #include <unordered_map>
-#include <utility>
 
 namespace dllm {
 
 namespace {
-constexpr int PBK = 64;                       // K per ring slot (128-byte rows)
-typedef __attribute__((address_space(3))) void* lds_vptr_p;
-typedef __attribute__((address_space(1))) void* glb_vptr_p;
-
-__device__ __forceinline__ int pswz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-template <int OFF>
-__device__ __forceinline__ bf16x8 pp_frag(uint32_t addr) {
-  bf16x8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "i"(OFF));
-  return r;
-}
-
 // fragment read at an LDS byte address, in inline asm: hipcc does not count it, so the only waits
 // are the counted ones of PpSched (its own waitcnt insertion falls back to lgkmcnt(0) at the loop
 // head and before every MFMA that uses a read from the previous iteration)
@@ -71,34 +57,6 @@ __device__ __forceinline__ void pp_wait_n(int younger) {   // younger: compile-t
   else { if (younger == 1) PP_VM(16); else PP_VM(32); }
 }
 #undef PP_VM
-
-// s_waitcnt vmcnt(N) for a compile-time N
-template <int N>
-__device__ __forceinline__ void pp_vm() {
-  static_assert(N >= 0 && N <= 63, "vmcnt");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
-// f(integral_constant<int, i>) for i = 0 .. N-1, each i a constant expression
-template <int... I, class F>
-__device__ __forceinline__ void pp_static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void pp_static_for(F&& f) {
-  pp_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
-
-// s_waitcnt lgkmcnt(N) for a compile-time N (16 = no wait); a sched_barrier keeps hipcc from
-// hoisting register-only MFMAs above an inline-asm wait (guide rule 18)
-template <int N>
-__device__ __forceinline__ void pp_lgkm() {
-  static_assert(N >= 0 && N <= 16, "lgkmcnt");
-  if constexpr (N < 16) {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
 
 // Fragment-read schedule of one K-half (RT A-fragments, CT B-fragments; MFMA i uses A r = i / CT,
 // B c = i % CT).  The reads for the OTHER K-half go out after MFMA pos(): A fragment a right after
@@ -692,10 +650,6 @@ void gemm_pp_moe(uintptr_t y, uintptr_t x, uintptr_t gather, uintptr_t w, uintpt
 // SCH 8: nontemporal output stores (large SwiGLU outputs), else 0.  The schedule sweeps of rounds 3-5
 // (barrier positions, piece spacing, row-group widths, and the split A / B LDS release of round 5,
 // all within 0.5 % of this schedule: profiles/round5_raw/r5d_pf_sched.txt) were removed.
-struct PfSched {
-  int ib1, ib3, ge, gm;
-};
-
 // ---- gemm_pf's dynamic tile queue (DYN).  The grouped tile order is cut into chunks of PF_CH
 // consecutive tiles (8 row tiles x 4 column tiles); chunk c belongs to XCD c % 8, whose workgroups
 // pull its tiles in order from the XCD's head counter (one 128-byte line each) and, when it is
@@ -749,10 +703,6 @@ __device__ void pf_retire(int* q, int grid) {                      // lane 0, on
     __hip_atomic_store(q + 256, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-// {barrier after set-1 reads (MFMA), barrier before set-0 reads, MFMAs between pieces (0 = spread
-// over the rest of the K-tile), row tiles per group of the tile order}
-constexpr PfSched kPfSched{40, 88, 0, 8};
-
 template <int MODE, int SCH = 0, bool DYN = false>
 __global__ void __launch_bounds__(256, 1) gemm_pf_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                                                          bf16* __restrict__ C, int M, int N, int K,
@@ -889,26 +839,7 @@ __global__ void __launch_bounds__(256, 1) gemm_pf_kernel(const bf16* __restrict_
 
   f32x4 acc[RT][CT];
   bf16x8 fa0[RT], fb0[CT], fa1[RT], fb1[CT];
-  constexpr int NMF = RT * CT, NR = RT + CT;
-  constexpr PfSched SC = kPfSched;
-  constexpr int IB1 = SC.ib1;
-  constexpr int GE = SC.ge ? SC.ge : ((2 * NMF - 4 - IB1 - 1) / G > 1 ? (2 * NMF - 4 - IB1 - 1) / G : 1);
-  constexpr int IB3 = SC.ib3;
-  static_assert(IB1 > 2 * NR - 1 && IB1 < NMF && IB3 >= NMF, "schedule 2 barriers");
-  constexpr int PB3 = (IB3 - IB1 - 1) / GE + 1 < G ? (IB3 - IB1 - 1) / GE + 1 : G;
-  constexpr int VC = (NB - 2) * G + PB3;
-  static_assert(IB1 + 1 + GE * (G - 1) < 2 * NMF && IB3 + 1 + 2 * (NR - 1) < 2 * NMF, "schedule 2 fits a K-tile");
-  static_assert(VC <= 63, "vmcnt");
-  auto rd0 = [&](uint32_t base, auto mc) {
-    constexpr int m = decltype(mc)::value;
-    if constexpr (m < CT) fb0[m] = pp_frag<m * 16 * 128>(base + b_off);
-    else fa0[m - CT] = pp_frag<(m - CT) * 16 * 128>(base + a_off);
-  };
-  auto rd1 = [&](uint32_t base, auto mc) {
-    constexpr int m = decltype(mc)::value;
-    if constexpr (m < CT) fb1[m] = pp_frag<m * 16 * 128>(base + b_off);
-    else fa1[m - CT] = pp_frag<(m - CT) * 16 * 128>(base + a_off);
-  };
+  using KT = PfKtile<RT, CT, G, NB>;                   // schedule 2's K-tile (gemm_pp_loop.h)
 
   // prologue: the first NB K-tiles of my first tile in flight, K-tile 0 landed, its K-half 0 read
   set_stage(tile_of(0));
@@ -921,8 +852,7 @@ __global__ void __launch_bounds__(256, 1) gemm_pf_kernel(const bf16* __restrict_
   pp_vm<(NB - 1) * G>();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  pp_static_for<NR>([&](auto mc) { rd0(lds_base + lane_off[0], mc); });
-  __builtin_amdgcn_sched_barrier(0);
+  KT::read_first(fa0, fb0, lds_base + lane_off[0], a_off, b_off);
 
   const int lr = lane & 15, lq = lane >> 4;
   int slot = 0;
@@ -941,32 +871,7 @@ __global__ void __launch_bounds__(256, 1) gemm_pf_kernel(const bf16* __restrict_
       const int nslot = slot == NB - 1 ? 0 : slot + 1;
       const uint32_t base1 = lds_base + (uint32_t)(slot * SLOT * 2) + lane_off[1];
       const uint32_t base0 = lds_base + (uint32_t)(nslot * SLOT * 2) + lane_off[0];
-      pp_static_for<2 * NMF>([&](auto ic) {
-        constexpr int i = decltype(ic)::value, h = i / NMF, j = i % NMF, r = j / CT, c = j % CT;
-        if constexpr (h == 0 && c == 0) {
-          constexpr int w0 = (RT - 1 - r) + (j / 2 < NR ? j / 2 : NR);
-          pp_lgkm<(w0 > 15 ? 15 : w0)>();
-        }
-        if constexpr (h == 0)
-          acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb0[c], fa0[r], acc[r][c], 0, 0, 0);
-        else
-          acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb1[c], fa1[r], acc[r][c], 0, 0, 0);
-        if constexpr (i % 2 == 1 && i / 2 < NR) rd1(base1, std::integral_constant<int, i / 2>{});
-        if constexpr (i == IB1) {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          __builtin_amdgcn_s_barrier();
-        }
-        if constexpr (i > IB1 && (i - IB1 - 1) % GE == 0 && (i - IB1 - 1) / GE < G) piece(slot, (i - IB1 - 1) / GE);
-        if constexpr (i == IB3) {
-          pp_vm<VC>();
-          __builtin_amdgcn_sched_barrier(0);
-          __builtin_amdgcn_s_barrier();
-        }
-        if constexpr (i > IB3 && (i - IB3 - 1) % 2 == 0 && (i - IB3 - 1) / 2 < NR)
-          rd0(base0, std::integral_constant<int, (i - IB3 - 1) / 2>{});
-        __builtin_amdgcn_sched_barrier(0);
-      });
+      KT::run(acc, fa0, fb0, fa1, fb1, base0, base1, a_off, b_off, [&](int p) { piece(slot, p); });
       advance();
       slot = nslot;
     }

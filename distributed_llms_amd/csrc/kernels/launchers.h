@@ -74,6 +74,12 @@ int gemm_pp(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats,
 void gemm_pp_moe(uintptr_t y, uintptr_t x, uintptr_t gather, uintptr_t w, uintptr_t counts, uintptr_t offsets, int E,
                  int N, int K, int xrows, int slots, int mode, uintptr_t stream);
 void gemm_pf(uintptr_t c, uintptr_t a, uintptr_t b, int M, int N, int K, int mode, int variant, uintptr_t stream);
+// lm_head_logprobs.hip: out[i] = log softmax(bf16(x_i . w^T))[targets[i]] with no logits stored.  out f32 [T], x bf16
+// [T, K], w bf16 [V, K], targets i32 [T] (< 0: the row is skipped, out 0); S vocabulary ranges (grid = row tiles x S);
+// ws: f32 [T, kLmHeadWaves * S, 3] partial (max, sum, target logit) triples
+constexpr int kLmHeadWaves = 2;
+void lm_head_logprobs(uintptr_t out, uintptr_t x, uintptr_t w, uintptr_t targets, uintptr_t ws, long ws_floats, int T,
+                      int V, int K, int S, uintptr_t stream);
 int gemm_sq(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats, int M, int N, int K, int splits,
             int mode, int variant, uintptr_t stream);
 

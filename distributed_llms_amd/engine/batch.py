@@ -64,6 +64,14 @@ class HostBatch:
     # adapter -- the packed array is then what it was without the field and no LoRA kernel runs.
     # Packed after the processors section with header word 13 set
     lora: Optional[np.ndarray] = None
+    # prompt scoring (SamplingParams.prompt_logprobs): ``score_idx`` [n] int32, the step's rows whose next
+    # prompt token gets its log-probability, and ``score_targets`` [n] int32, those tokens; None when no
+    # prefill row of the step asks -- the packed array is then what it was without the fields and nothing
+    # new is launched.  Packed [n | idx | targets] after the lora section with header word 14 set
+    score_idx: Optional[np.ndarray] = None
+    score_targets: Optional[np.ndarray] = None
+    # the sampling stage's result for those rows, float32 [n] on its device (StageRunner.execute)
+    prompt_lp: Optional[torch.Tensor] = field(default=None, repr=False, compare=False)
 
     @property
     def num_tokens(self) -> int:
@@ -87,8 +95,9 @@ class HostBatch:
         has_lp = 1 if self.logprobs is not None else 0
         has_pr = 1 if self.procs is not None else 0
         has_lo = 1 if self.lora is not None else 0
+        has_sc = 1 if self.score_idx is not None else 0
         hdr = np.array([1 if self.is_prefill else 0, t, b, mb, self.max_q_len, self.max_ctx, self.slot,
-                        self.step_id, has_s, self.num_decode, has_seeds, has_lp, has_pr, has_lo] + [0] * 2,
+                        self.step_id, has_s, self.num_decode, has_seeds, has_lp, has_pr, has_lo, has_sc] + [0],
                        dtype=np.int32)
         parts = [hdr, self.ids, self.positions, self.slots, self.seq_lens, self.cu_seqlens,
                  self.block_tables.reshape(-1), self.logits_idx]
@@ -103,6 +112,8 @@ class HostBatch:
                       self.bias_ids, self.bias_vals]
         if has_lo:
             parts.append(self.lora)
+        if has_sc:
+            parts += [np.array([self.score_idx.shape[0]], dtype=np.int32), self.score_idx, self.score_targets]
         return np.concatenate([p.astype(np.int32, copy=False).reshape(-1) for p in parts])
 
     def sampling_args(self) -> dict:
@@ -143,6 +154,9 @@ class HostBatch:
             hb.bias_ids, hb.bias_vals = take(nb), take(nb)
         if int(hdr[13]):
             hb.lora = take(b)
+        if int(hdr[14]):
+            n = int(take(1)[0])
+            hb.score_idx, hb.score_targets = take(n), take(n)
         return hb
 
 
@@ -186,6 +200,24 @@ def attach_lora(hb: HostBatch, seqs) -> None:
     if not any(s.lora_slot >= 0 for s in seqs):
         return
     hb.lora = np.fromiter((s.lora_slot for s in seqs), dtype=np.int32, count=len(seqs))
+    hb.raw = None            # a natively packed batch: pack() concatenates again, section included
+
+
+def attach_scores(hb: HostBatch, seqs) -> None:
+    """Give the prefill batch ``hb`` its prompt-scoring section when a row of it asks: for every position
+    ``Sequence.score_positions`` names, the row that computes it and the prompt token that follows.
+    ``seqs``: the batch's sequences in row order."""
+    if not any(s.prompt_logprobs is not None for s in seqs):
+        return
+    idx, tgt = [], []
+    for i, s in enumerate(seqs):
+        base = int(hb.cu_seqlens[i]) - s.num_cached
+        for p in s.score_positions():
+            idx.append(base + p)
+            tgt.append(s.prompt[p + 1])
+    if not idx:
+        return
+    hb.score_idx, hb.score_targets = np.asarray(idx, dtype=np.int32), np.asarray(tgt, dtype=np.int32)
     hb.raw = None            # a natively packed batch: pack() concatenates again, section included
 
 
@@ -282,6 +314,8 @@ def build_host_batch(step: Step, bm, block_size: int, max_blocks: Optional[int] 
         attach_procs(hb, seqs, state_rows, step.is_prefill)
     if lora:
         attach_lora(hb, seqs)
+    if step.is_prefill:
+        attach_scores(hb, seqs)
     return hb
 
 
@@ -335,6 +369,8 @@ def merge_mixed(dec: HostBatch, pre: HostBatch, slot: int, step_id: int) -> Host
         hb.lora = np.concatenate([dec.lora if dec.lora is not None else np.full(nd, -1, np.int32),
                                   pre.lora if pre.lora is not None
                                   else np.full(pre.num_seqs, -1, np.int32)]).astype(np.int32)
+    if pre.score_idx is not None:      # the chunks' rows follow the nd decode rows
+        hb.score_idx, hb.score_targets = (pre.score_idx + nd).astype(np.int32), pre.score_targets
     return hb
 
 
@@ -385,4 +421,6 @@ def to_device_meta(hb: HostBatch, device, pad_ctx_to: Optional[int] = None) -> (
     if hb.lora is not None:
         from ..ops import lora
         meta.lora = lora.make_plan(token_lora_slots(hb), dev)
+    if hb.score_idx is not None:
+        meta.score_idx, meta.score_targets = up(hb.score_idx, torch.int64), up(hb.score_targets)
     return ids, meta

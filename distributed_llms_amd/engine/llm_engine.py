@@ -23,12 +23,14 @@ from ..models.stage import ModelStage
 from .batch import build_host_batch
 from .graphs import SCRATCH_SEQ_ID
 from .runner import StageRunner
-from .sampler import ids_message_len, max_ids_message_len, sample_step, unpack_ids_message
+from .sampler import (ids_message_len, max_ids_message_len, sample_step, unpack_ids_message,
+                      unpack_prompt_logprobs)
 from .scheduler import Scheduler, Step
 from .logit_state import LogitState
 from ..models.lora import adapter_slots
 from .sequence import (SamplingParams, Sequence, fused_sampler_serves, request_seed, resolve_adapter,
-                       validate_logprobs, validate_processors, validate_sampling)
+                       check_prompt_logprobs_head, validate_logprobs, validate_processors, validate_prompt_logprobs,
+                       validate_sampling)
 
 log = logging.getLogger("dllm.engine")
 
@@ -103,8 +105,8 @@ class LLMEngine:
             dev = self.stage.device
             self.streams = [torch.cuda.Stream(dev) for _ in range(self.num_slots)]
             # two pinned token buffers + events per slot: with lookahead two steps of a slot are in flight
-            self.tok_host = [[torch.empty(max_ids_message_len(max(ecfg.max_batch, 1)), dtype=torch.int32).pin_memory()
-                              for _ in range(2)]
+            msg_len = max_ids_message_len(max(ecfg.max_batch, 1), ecfg.max_prefill_tokens)
+            self.tok_host = [[torch.empty(msg_len, dtype=torch.int32).pin_memory() for _ in range(2)]
                              for _ in range(self.num_slots)]
             self.events = [[torch.cuda.Event() for _ in range(2)] for _ in range(self.num_slots)]
             self.tok_i = [0] * self.num_slots
@@ -117,6 +119,10 @@ class LLMEngine:
             # the tensor-parallel lanes draw with a distributed arg-max over vocabulary shards;
             # log-probabilities there need a distributed log-sum-exp
             raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
+        if validate_prompt_logprobs(params.prompt_logprobs):
+            if self.tp is not None:      # the lanes hold vocabulary shards: the log-sum-exp would be distributed
+                raise ValueError("prompt_logprobs are not supported with tensor parallelism (tp > 1)")
+            check_prompt_logprobs_head(self.stage.lm_head_weight())
         if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
             # the processors rewrite whole logit rows; the tensor-parallel lanes hold vocabulary shards
             raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
@@ -149,14 +155,15 @@ class LLMEngine:
         return self._execute(step)[0].tolist()
 
     def _execute(self, step: Step):
-        """Synchronous execution of one step -> (ids, logprobs) on the host, as
-        ``Scheduler.complete`` takes them (``logprobs`` None unless a row of the step asked)."""
+        """Synchronous execution of one step -> (ids, logprobs, prompt_lp) on the host, as
+        ``Scheduler.complete`` takes them (``logprobs`` / ``prompt_lp`` None unless a row of the step asked)."""
         hb = self._host_batch(step)
         logits = self.runner.execute(hb, slot=step.slot)
         ids, msg = self._sample(logits, hb)
         if msg is None:
-            return ids.cpu().numpy(), None
-        return unpack_ids_message(msg.cpu().numpy(), hb)
+            return ids.cpu().numpy(), None, None
+        msg = msg.cpu().numpy()
+        return (*unpack_ids_message(msg, hb), unpack_prompt_logprobs(msg, hb))
 
     def _sample(self, logits, hb):
         """(ids, ids message or None): engine/sampler.py sample_step."""
@@ -221,8 +228,9 @@ class LLMEngine:
         if lp_hb is None:
             self.scheduler.complete(step, self.tok_host[slot][i][:n].numpy(), time.perf_counter())
         else:     # a row of the step asked for log-probabilities: the pinned buffer holds its ids message
-            toks, lps = unpack_ids_message(self.tok_host[slot][i][:ids_message_len(lp_hb)].numpy(), lp_hb)
-            self.scheduler.complete(step, toks, time.perf_counter(), lps)
+            msg = self.tok_host[slot][i][:ids_message_len(lp_hb)].numpy()
+            toks, lps = unpack_ids_message(msg, lp_hb)
+            self.scheduler.complete(step, toks, time.perf_counter(), lps, unpack_prompt_logprobs(msg, lp_hb))
         self.busy[slot] = any(e[1] == slot for e in self.inflight)
 
     def step(self) -> List[Sequence]:
@@ -230,8 +238,8 @@ class LLMEngine:
         if self.stage.device.type != "cuda":
             st = self.scheduler.schedule(0)
             if st is not None:
-                toks, lps = self._execute(st)
-                self.scheduler.complete(st, toks, time.perf_counter(), lps)
+                toks, lps, plp = self._execute(st)
+                self.scheduler.complete(st, toks, time.perf_counter(), lps, plp)
             return self.scheduler.pop_finished()
         issued = False
         for slot in range(self.num_slots):

@@ -100,7 +100,9 @@ class StageRunner:
         ids, meta = to_device_meta(hb, st.device)
         if ids_dev is not None:
             ids = ids_dev.to(torch.int32)
-        return st.forward(ids if st.is_first else hidden, meta)
+        out = st.forward(ids if st.is_first else hidden, meta)
+        hb.prompt_lp = meta.prompt_lp      # prompt scoring: the asking rows' values, behind the ids in the message
+        return out
 
     # ---- busy metering: the stage's device time per microbatch (bench.py's stage_busy_frac)
     def meter(self, on: bool = True):

@@ -107,20 +107,28 @@ def _sample_seeded(logits, temperatures, top_k, top_p, seeds, positions) -> torc
 #     [ids B | chosen B (f32 bits) | top_ids B*N | top_lp B*N (f32 bits)],  N = max(hb.logprobs)
 # With N = 0 the two top sections are empty; rows that did not ask hold the kernel's filler.  A
 # step without an asking row sends its ids alone, as before.
+#
+# A step with a prompt-scoring section (``hb.score_idx`` is not None) appends the n log-probabilities of
+# its scored rows (f32 bits), behind whichever of the two forms above it answers with.
 def _top_n(hb) -> int:
     return max(0, int(hb.logprobs.max()))
+
+
+def _num_scored(hb) -> int:
+    return 0 if hb.score_idx is None else int(hb.score_idx.shape[0])
 
 
 def ids_message_len(hb) -> int:
     """int32 words the last stage answers a step with (both ends of a pipeline size by this)."""
     b = hb.num_seqs
-    return b if hb.logprobs is None else b * (2 + 2 * _top_n(hb))
+    return (b if hb.logprobs is None else b * (2 + 2 * _top_n(hb))) + _num_scored(hb)
 
 
-def max_ids_message_len(max_batch: int) -> int:
+def max_ids_message_len(max_batch: int, max_scored: int = 0) -> int:
     """The longest ids message of a step of ``max_batch`` rows: every row asking for MAX_LOGPROBS
-    entries.  Transports with fixed ids slots (RcclTransport's ``max_ids``) are sized by it."""
-    return int(max_batch) * (2 + 2 * MAX_LOGPROBS)
+    entries, plus ``max_scored`` prompt log-probabilities (an engine that serves prompt_logprobs: its
+    prefill token budget).  Transports with fixed ids slots (RcclTransport's ``max_ids``) are sized by it."""
+    return int(max_batch) * (2 + 2 * MAX_LOGPROBS) + int(max_scored)
 
 
 def pack_ids_message(ids, chosen, top_ids, top_lp) -> torch.Tensor:
@@ -135,6 +143,7 @@ def unpack_ids_message(msg: np.ndarray, hb):
     msg = np.asarray(msg, dtype=np.int32)
     if msg.shape[0] != ids_message_len(hb):
         raise ValueError(f"ids message of {msg.shape[0]} words, expected {ids_message_len(hb)}")
+    msg = msg[:msg.shape[0] - _num_scored(hb)]
     if hb.logprobs is None:
         return msg, None
     n = _top_n(hb)
@@ -142,7 +151,25 @@ def unpack_ids_message(msg: np.ndarray, hb):
                      msg[(2 + n) * b:].view(np.float32).reshape(b, n))
 
 
+def unpack_prompt_logprobs(msg: np.ndarray, hb) -> Optional[np.ndarray]:
+    """The prompt log-probabilities at the end of a step's ids message (float32 [n], in the order of
+    ``hb.score_idx``); None for a step without a prompt-scoring section."""
+    n = _num_scored(hb)
+    return np.asarray(msg, dtype=np.int32)[-n:].view(np.float32) if n else None
+
+
 def sample_step(logits: torch.Tensor, hb, state=None, eos_id: Optional[int] = None):
+    """``_sample_step`` plus the step's prompt log-probabilities (``hb.prompt_lp``, left by the stage
+    executor) behind its message; a step without a prompt-scoring section answers as before."""
+    ids, msg = _sample_step(logits, hb, state, eos_id)
+    if hb.score_idx is None:
+        return ids, msg
+    if hb.prompt_lp is None:
+        raise ValueError("sample_step: the step has a prompt-scoring section but the stage left no result")
+    return ids, torch.cat([(ids if msg is None else msg).to(torch.int32), hb.prompt_lp.view(torch.int32)])
+
+
+def _sample_step(logits: torch.Tensor, hb, state=None, eos_id: Optional[int] = None):
     """Sample a step's rows -> (ids [B] int32, message).  ``message`` is None unless a row of the
     step asked for log-probabilities; then it is the ids message above: one more kernel
     (``ops.token_logprobs``) over the logits the ids were drawn from.

@@ -290,8 +290,10 @@ class Scheduler:
         deferred: List[Sequence] = []       # passed over for a pending key; they keep their queue position
         while self.waiting and n_running + len(admitted) < target:
             seq = self.waiting[0]
-            # a sequence with a LoRA adapter neither queries nor registers blocks: its K/V depend on the adapter
-            if self.prefix and seq.lora_slot < 0 and seq.num_cached == 0 and not self.bm.has_sequence(seq.seq_id):
+            # a sequence with a LoRA adapter neither queries nor registers blocks: its K/V depend on the adapter;
+            # one that asks for prompt_logprobs does not query (a hit skips the rows it scores) but registers
+            if self.prefix and seq.lora_slot < 0 and seq.prompt_logprobs is None and seq.num_cached == 0 \
+                    and not self.bm.has_sequence(seq.seq_id):
                 toks = self._tokens(seq)
                 if self._gains_by_waiting(toks):
                     deferred.append(self.waiting.popleft())
@@ -448,15 +450,32 @@ class Scheduler:
                 n = seq.params.logprobs
                 seq.logprobs.append((float(chosen[i]), top_ids[i, :n].tolist(), top_lp[i, :n].tolist()))
 
-    def complete(self, step: Step, tokens, now: Optional[float] = None, logprobs=None) -> List[Sequence]:
+    def complete(self, step: Step, tokens, now: Optional[float] = None, logprobs=None,
+                 prompt_lp=None) -> List[Sequence]:
         """Apply sampled tokens of an executed step; returns sequences that finished.  ``logprobs``:
         (chosen [B], top_ids [B, N], top_lp [B, N]) of the step's rows when one of them asked
-        (engine/sampler.py unpack_ids_message), else None."""
+        (engine/sampler.py unpack_ids_message), else None.  ``prompt_lp``: the step's prompt
+        log-probabilities (unpack_prompt_logprobs), None for a step that scored nothing."""
         now = time.perf_counter() if now is None else now
         try:
+            if prompt_lp is not None:
+                self._record_prompt_lp(step, prompt_lp)
             return self._complete(step, tokens, now, logprobs)
         finally:
             self._completed += 1
+
+    @staticmethod
+    def _record_prompt_lp(step: Step, prompt_lp) -> None:
+        """The values of the step's prompt-scoring section, to the sequences that asked: the order in
+        which engine/batch.py attach_scores listed them (each sequence's score_positions, before this
+        step's completion moves num_cached)."""
+        o = 0
+        for seq in step.seqs:
+            for p in seq.score_positions():
+                seq.prompt_logprobs[p + 1] = float(prompt_lp[o])
+                o += 1
+        if o != len(prompt_lp):
+            raise ValueError(f"{len(prompt_lp)} prompt log-probabilities for {o} scored rows")
 
     def _complete(self, step: Step, tokens, now: float, logprobs) -> List[Sequence]:
         if not step.is_prefill:

@@ -33,6 +33,9 @@ class SamplingParams:
     # per-token log-probabilities of the model's distribution: None = off, 0 = the chosen token's
     # only, 1..MAX_LOGPROBS = that many most likely alternatives too (validate_logprobs)
     logprobs: Optional[int] = None
+    # the log-probability the model gives every prompt token after the first (validate_prompt_logprobs):
+    # the fused LM-head log-likelihood kernel over all prefill rows, ``Sequence.prompt_logprobs``
+    prompt_logprobs: bool = False
     # logit processors (validate_processors; contract in ops/reference.py), applied to the logits
     # before greedy / sampled selection and before logprobs are taken.  The defaults mean "off"
     repetition_penalty: float = 1.0     # > 0; over prompt + output tokens
@@ -68,6 +71,25 @@ def validate_logprobs(value) -> Optional[int]:
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= MAX_LOGPROBS:
         raise ValueError(f"logprobs must be an integer from 0 to {MAX_LOGPROBS}, got {value!r}")
     return value
+
+
+def validate_prompt_logprobs(value) -> bool:
+    """``SamplingParams.prompt_logprobs`` as the engines take it: a bool (None counts as False);
+    anything else raises ValueError."""
+    if value is None:
+        return False
+    if not isinstance(value, bool):
+        raise ValueError(f"prompt_logprobs must be true or false, got {value!r}")
+    return value
+
+
+def check_prompt_logprobs_head(weight) -> None:
+    """The fused LM-head log-likelihood op takes a plain bf16 / float weight [V, K]: an asking request on a
+    sampling stage with anything else (a quantised LM head) is refused when it is admitted (ValueError)."""
+    import torch
+    if not isinstance(weight, torch.Tensor) or not weight.is_floating_point() or weight.element_size() < 2:
+        raise ValueError("prompt_logprobs are not supported with a quantised LM head: the sampling stage's LM-head "
+                         "weight must be a plain bf16 or float tensor")
 
 
 SAMPLE_MAX_VOCAB = 131072      # ops.SAMPLE_MAX_VOCAB: the row the fused sampler holds in registers
@@ -221,18 +243,35 @@ class Sequence:
     prefix_queried: bool = False
     # the slot of params.adapter among the engine's adapters (resolve_adapter), -1: the base model
     lora_slot: int = -1
+    # requests with params.prompt_logprobs: [None, lp_1, ..., lp_{P-1}], lp_p the log-probability of
+    # prompt[p] given prompt[:p]; filled chunk by chunk as the prefill steps complete (an entry still
+    # None is not yet computed), None for a request that did not ask
+    prompt_logprobs: Optional[List[Optional[float]]] = None
     prompt_i32: Optional[Any] = field(default=None, repr=False, compare=False)
 
     def __post_init__(self):
         if not self.prompt:
             raise ValueError("empty prompt")
         self.prompt = [int(t) for t in self.prompt]
+        if self.params.prompt_logprobs:
+            self.prompt_logprobs = [None] * len(self.prompt)
 
     @property
     def num_logprobs(self) -> int:
         """The row's ``HostBatch.logprobs`` word: -1 when the request did not ask."""
         n = self.params.logprobs
         return -1 if n is None else int(n)
+
+    def score_positions(self) -> List[int]:
+        """The positions of the current prefill step's rows whose NEXT token is a prompt token without a
+        recorded log-probability yet: what the step scores (row p predicts prompt[p + 1]).  A prefill
+        recomputed after a preemption finds its positions recorded and scores nothing; output tokens
+        (positions >= P - 1) are never scored."""
+        lp = self.prompt_logprobs
+        if lp is None:
+            return []
+        a = self.num_cached
+        return [p for p in range(a, min(a + self.prefill_len, len(self.prompt) - 1)) if lp[p + 1] is None]
 
     @property
     def total_len(self) -> int:

@@ -20,6 +20,13 @@ dependency; every request thread only submits to the master's request futures):
                                "token_logprobs", "top_logprobs": [{text: lp}], "text_offset"} plus
                                "token_ids" / "top_token_ids" (two ids can decode to the same text);
                                -inf is serialised as null
+  "prompt_logprobs": true      (either POST, not with "stream": 400) the log-probability the model gives each
+                               prompt token after the first: "prompt_logprobs": [null, lp_1, ..., lp_{P-1}] in the
+                               /generate reply and in every choice of /v1/completions (with "n" every child
+                               carries the same list); -inf is serialised as null.  Refused (400) with tensor
+                               parallelism, on a pipeline of more than one stage and with a quantised LM head
+  refusals                     whatever the front end, the master or the stage-0 engine refuses when it admits a
+                               request (a ValueError there) is a 400; other worker errors and timeouts are a 503
   logit processors             (either POST, also with "stream") "repetition_penalty" (> 0, over prompt and
                                output tokens), "presence_penalty" / "frequency_penalty" ([-2, 2], over output
                                tokens), "logit_bias" ({"token id": bias in [-100, 100]}, at most 300 entries,
@@ -54,12 +61,12 @@ import time
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from typing import Any, Dict, List, Tuple
 
-from ..engine.sequence import PROCESSOR_KEYS, validate_logprobs, validate_processors
+from ..engine.sequence import PROCESSOR_KEYS, validate_logprobs, validate_processors, validate_prompt_logprobs
 from ..utils.metrics import cluster_prometheus_text
 
 log = logging.getLogger("dllm.http")
 
-_PARAM_KEYS = ("temperature", "top_k", "top_p", "ignore_eos", "seed", "logprobs") + PROCESSOR_KEYS
+_PARAM_KEYS = ("temperature", "top_k", "top_p", "ignore_eos", "seed", "logprobs", "prompt_logprobs") + PROCESSOR_KEYS
 
 
 def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_new_tokens",
@@ -79,6 +86,8 @@ def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_n
     validate_logprobs(p.get("logprobs"))
     if p.get("logprobs") is not None and body.get("stream"):
         raise ValueError("logprobs are not available with stream")
+    if validate_prompt_logprobs(p.get("prompt_logprobs")) and body.get("stream"):
+        raise ValueError("prompt_logprobs are not available with stream")
     validate_processors(p, vocab_size)       # logit_bias arrives with string keys: {int: float} from here on
     return p
 
@@ -261,6 +270,10 @@ class _Handler(BaseHTTPRequestHandler):
             r["text"] = m.tokenizer.decode(r["tokens"])
             if r.get("logprobs") is None:
                 r.pop("logprobs", None)                # a request that did not ask: the reply it always got
+            if r.get("prompt_logprobs") is None:
+                r.pop("prompt_logprobs", None)         # likewise
+            else:
+                r["prompt_logprobs"] = [None if x is None else _finite(x) for x in r["prompt_logprobs"]]
             if not r.get("cached_tokens"):
                 r.pop("cached_tokens", None)           # no hit (or no cache): likewise
             out.append(r)
@@ -294,6 +307,8 @@ class _Handler(BaseHTTPRequestHandler):
         for c, r in zip(choices, res):
             if "logprobs" in r:
                 c["logprobs"] = _openai_logprobs(self.master.tokenizer, r["tokens"], r["logprobs"])
+            if "prompt_logprobs" in r:
+                c["prompt_logprobs"] = r["prompt_logprobs"]
         ptok = sum(len(p) for p in prompts)
         ctok = sum(len(r["tokens"]) for r in res)
         return {"id": res[0].get("task_id"), "object": "text_completion", "created": int(time.time()),

@@ -33,9 +33,9 @@ from typing import Any, Dict, List, Optional, Sequence
 
 from ..config import EngineConfig, ModelConfig, get_model_config
 from ..engine.sequence import (fused_sampler_serves, resolve_adapter, validate_logprobs, validate_processors,
-                               validate_sampling)
+                               validate_prompt_logprobs, validate_sampling)
 from ..models.lora import adapter_slots
-from ..network.protocol import MessageProtocol, pack_ids, unpack_ids, unpack_result
+from ..network.protocol import MessageProtocol, pack_ids, split_prompt_logprobs, unpack_ids, unpack_result
 from ..utils.metrics import RequestMetrics
 from ..utils.tokenizer import get_tokenizer
 
@@ -197,8 +197,9 @@ class MasterNode:
                 fut = self._tasks.pop(header.get("task_id"), None)
                 self._reqs.pop(header.get("task_id"), None)
             if fut and not fut.done():
+                payload, plp = split_prompt_logprobs(payload, header.get("prompt_logprobs"))
                 ids, lps = unpack_result(payload, header.get("num_tokens"), header.get("logprobs"))
-                fut.set_result((dict(header, logprobs=lps), ids))
+                fut.set_result((dict(header, logprobs=lps, prompt_logprobs=plp), ids))
             q = self._streams.get(header.get("task_id"))
             if q is not None:
                 q.put(None)                         # the stream's end: the full ids are in the future
@@ -212,7 +213,8 @@ class MasterNode:
                 fut = self._tasks.pop(header.get("task_id"), None) if header.get("task_id") else None
                 self._reqs.pop(header.get("task_id"), None)
             if fut and not fut.done():
-                fut.set_exception(RuntimeError(header.get("error")))
+                # a request the stage-0 engine refused at admission stays a ValueError (HTTP: 400)
+                fut.set_exception((ValueError if header.get("refused") else RuntimeError)(header.get("error")))
             ack = self._acks.get(worker_id)
             if header.get("failed_command") == "LOAD_SHARD" and ack and not ack.done():
                 ack.set_exception(RuntimeError(f"{worker_id} failed to load its shard: {header.get('error')}"))
@@ -537,6 +539,12 @@ class MasterNode:
         validate_logprobs(params.get("logprobs"))      # a bad value fails here, not on the stage-0 worker
         if params.get("logprobs") is not None and params.get("stream"):
             raise ValueError("logprobs are not available with stream")
+        if validate_prompt_logprobs(params.get("prompt_logprobs")):
+            # refused here, at admission, never inside a running step (the stage-0 worker checks again)
+            if params.get("stream"):
+                raise ValueError("prompt_logprobs are not available with stream")
+            if len(self.stage_workers) > 1:
+                raise ValueError("prompt_logprobs are not supported on a pipeline of more than one stage")
         validate_processors(params, self.model_config.vocab_size if self.model_config else 1 << 31)     # normalises logit_bias to {int: float}
         resolve_adapter(params.get("adapter"), adapter_slots(self.config))     # an unknown name fails here, before dispatch
         if self.model_config:      # by the configured device; a worker on another device checks again (worker/node.py)
@@ -618,6 +626,7 @@ class MasterNode:
         self.metrics.record(len(ids), lat, header.get("ttft_s"))
         return {"task_id": header.get("task_id"), "tokens": ids, "finish_reason": header.get("finish_reason"),
                 "latency_s": lat, "ttft_s": header.get("ttft_s"), "logprobs": header.get("logprobs"),
+                "prompt_logprobs": header.get("prompt_logprobs"),
                 "cached_tokens": int(header.get("cached_tokens") or 0)}
 
     def run_inference(self, input_text, timeout: float = 60, max_new_tokens: int = 32, **params) -> Dict[str, Any]:

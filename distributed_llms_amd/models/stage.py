@@ -58,6 +58,12 @@ class BatchMeta:
     # multi-LoRA (ops/lora.py LoraPlan): the step's per-token adapter slots and row plan, None when no
     # row of the step has an adapter -- the forward is then exactly the one without the feature
     lora: Optional[object] = None
+    # prompt scoring (SamplingParams.prompt_logprobs): the rows ``score_idx`` [n] int64 whose next prompt
+    # token ``score_targets`` [n] int32 gets its log-probability; the last stage leaves the result in
+    # ``prompt_lp`` (float32 [n]).  None when no row of the step asks: nothing new is launched
+    score_idx: Optional[torch.Tensor] = None
+    score_targets: Optional[torch.Tensor] = None
+    prompt_lp: Optional[torch.Tensor] = None
 
 
 class KVCache:
@@ -541,6 +547,8 @@ class ModelStage:
         cfg = self.cfg
         if meta.logits_idx is not None or cfg.arch == "gpt2":
             h = self._dense(h)
+        if meta.score_idx is not None:
+            self._score(h, residual, meta)
         if meta.logits_idx is not None:
             h = h.index_select(0, meta.logits_idx)
             residual = residual.index_select(0, meta.logits_idx)
@@ -549,6 +557,21 @@ class ModelStage:
         else:
             x, _ = ops.fused_add_rms_norm(h, residual, self.head["final_norm"], cfg.norm_eps)
         return ops.linear(x, self.lm_head_weight())
+
+    def _score(self, h: torch.Tensor, residual: Optional[torch.Tensor], meta: BatchMeta) -> None:
+        """Prompt scoring: the final norm over the asking rows of the last layer's output, then the fused
+        LM-head log-likelihood op with each row's next prompt token -- no logits of those rows exist."""
+        cfg = self.cfg
+        w = self.lm_head_weight()
+        if self.tp.enabled or not isinstance(w, torch.Tensor):
+            raise RuntimeError("prompt scoring needs the whole, plain LM head on the sampling stage")
+        h = h.index_select(0, meta.score_idx)
+        if cfg.arch == "gpt2":
+            x = ops.layer_norm(h, self.head["final_norm"], self.head["final_norm_b"], cfg.norm_eps)
+        else:
+            x, _ = ops.fused_add_rms_norm(h, residual.index_select(0, meta.score_idx), self.head["final_norm"],
+                                          cfg.norm_eps)
+        meta.prompt_lp = ops.lm_head_logprobs(x, w, meta.score_targets)
 
     def _forward_gpt2(self, inp: torch.Tensor, meta: BatchMeta) -> torch.Tensor:
         cfg = self.cfg
@@ -570,6 +593,8 @@ class ModelStage:
                 x = ops.add_(x, ops.linear(f, lw["w_proj"], lw["b_proj"]))
         if not self.is_last:
             return x
+        if meta.score_idx is not None:
+            self._score(x, None, meta)
         if meta.logits_idx is not None:
             x = x.index_select(0, meta.logits_idx)
         x = ops.layer_norm(x, self.head["final_norm"], self.head["final_norm_b"], eps)

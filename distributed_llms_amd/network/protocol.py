@@ -284,6 +284,26 @@ def pack_result(ids, logprobs=None, num_logprobs: Optional[int] = None) -> bytes
     return out + chosen.tobytes() + top_ids.tobytes() + top_lp.tobytes()
 
 
+def pack_prompt_logprobs(values) -> bytes:
+    """``Sequence.prompt_logprobs`` ([None, lp_1, ...]) as P float32 behind a RESULT's payload (pack_result);
+    an entry that is None travels as NaN.  The count P travels in the message's metadata."""
+    import numpy as np
+    return np.array([np.nan if x is None else x for x in values], dtype=np.float32).tobytes()
+
+
+def split_prompt_logprobs(b: Optional[bytes], count: Optional[int]):
+    """-> (the payload without its prompt log-probabilities, [None, lp_1, ...] or None): undoes
+    pack_prompt_logprobs for a RESULT whose metadata names ``count`` of them."""
+    import numpy as np
+    if count is None:
+        return b, None
+    n = 4 * int(count)
+    if b is None or len(b) < n:
+        raise ValueError(f"RESULT payload too short for {count} prompt log-probabilities")
+    vals = np.frombuffer(b[len(b) - n:], dtype=np.float32).tolist()
+    return b[:len(b) - n], [None if x != x else x for x in vals]
+
+
 def unpack_result(b: Optional[bytes], num_tokens: Optional[int] = None, num_logprobs: Optional[int] = None):
     """-> (ids list, logprobs): ``logprobs`` is None unless ``num_logprobs`` is given, else
     {"token_logprobs": [T floats], "top_ids": [T x n ints], "top_logprobs": [T x n floats]}."""

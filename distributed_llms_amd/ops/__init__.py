@@ -24,7 +24,8 @@ __all__ = [
     "embedding", "rms_norm", "fused_add_rms_norm", "layer_norm", "linear", "silu_mul",
     "gelu_tanh", "rope_cache_append", "paged_attention_decode", "paged_attention_prefill",
     "argmax", "add_", "moe_route", "moe_mlp", "decode_split_plan", "paged_attention_decode_rope",
-    "paged_attention_prefill_rope", "sample_rows", "token_logprobs", "logit_state_update",
+    "paged_attention_prefill_rope", "sample_rows", "token_logprobs", "lm_head_logprobs", "lm_head_ranges",
+    "logit_state_update",
     "apply_logit_processors", "logit_state_count", "prefill_split_plan", "prefill_split_eligible", "qkv_prep_",
 ]
 
@@ -319,6 +320,56 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, 
     _ext.kernels().token_logprobs(chosen.data_ptr(), top_ids.data_ptr(), top_lp.data_ptr(), logits.data_ptr(), rows, v,
                                   logits.stride(0), ids.data_ptr(), want.data_ptr(), n_max, _stream())
     return chosen, top_ids, top_lp
+
+
+def lm_head_ranges(t: int, v: int, cus: int = 256, comm_cus: Optional[int] = None) -> int:
+    """Vocabulary ranges S of the fused LM-head log-likelihood kernel: its grid is ceil(T / 256) row tiles x S,
+    about one workgroup per CU that no comm kernel may hold (ops/gemm.py), a range at least one 256-column tile."""
+    comm = gemm.comm_cus() if comm_cus is None else comm_cus
+    return max(1, min(-(-v // 256), (cus - comm) // -(-t // 256)))
+
+
+def lm_head_logprobs(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, ranges: int = 0) -> torch.Tensor:
+    """Log-probability the LM head gives each row's target token (contract: ops/reference.py lm_head_logprobs):
+    log_softmax(bf16(x w^T))[i, targets[i]] with linear, log-softmax and gather fused -- no [T, V] logits exist.
+
+    x [T, K]; w [V, K]; targets [T] int32 (negative: the row is skipped and gets 0.0) -> float32 [T].  bf16 CUDA
+    operands with K % 64 == 0 take the HIP kernel (csrc/kernels/lm_head_logprobs.hip: any T and V, partial triples
+    in the per-stream GEMM workspace, every value read on the device, graph-capturable, the same bits on every
+    launch); CPU tensors, other dtypes and everything with ``knobs.fused_sampler`` off take the reference, which
+    also refuses a target >= V.  The kernel cannot (it reads targets on the device only) and gives such a row -inf:
+    a caller that does not know its targets are below V checks them on the host first (the engine's are prompt
+    tokens, validated against the vocabulary by the embedding path).
+    ``ranges``: the kernel's vocabulary ranges (0: :func:`lm_head_ranges`)."""
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError(f"lm_head_logprobs: x [T, K] and w [V, K], got {tuple(x.shape)} and {tuple(w.shape)}")
+    t, k = x.shape
+    v = w.shape[0]
+    _ck(targets, "lm_head_logprobs.targets", torch.int32)
+    if targets.shape != (t,):
+        raise ValueError(f"lm_head_logprobs: targets must be [{t}]")
+    if w.device != x.device or targets.device != x.device:
+        raise ValueError("lm_head_logprobs: w and targets must be on x's device")
+    if t == 0:
+        return torch.empty(0, dtype=torch.float32, device=x.device)
+    if not (_gpu(x) and x.dtype == w.dtype == torch.bfloat16 and knobs.K.fused_sampler):
+        return ref.lm_head_logprobs(x, w, targets)
+    _ck(x, "lm_head_logprobs.x")
+    _ck(w, "lm_head_logprobs.w")
+    if k % 64 or k < 64 or t * k * 2 >= 1 << 32 or v * k * 2 >= 1 << 32:
+        raise ValueError("lm_head_logprobs: the kernel needs K % 64 == 0 and operands below 4 GiB")
+    s = int(ranges) or lm_head_ranges(t, v, gemm._cus(x.device))
+    if not 1 <= s <= -(-v // 256):
+        raise ValueError(f"lm_head_logprobs: ranges must be in [1, {-(-v // 256)}], got {s}")
+    ws = gemm._workspace(x.device)
+    need = t * _ext.kernels().LM_HEAD_WAVES * s * 3       # (m, l, target logit) per row, range and wave
+    if need > ws.numel():
+        raise ValueError(f"lm_head_logprobs: {t} rows x {s} ranges need {need} workspace floats, "
+                         f"the pool holds {ws.numel()}; score the rows in slices")
+    out = torch.empty(t, dtype=torch.float32, device=x.device)
+    _ext.kernels().lm_head_logprobs(out.data_ptr(), x.data_ptr(), w.data_ptr(), targets.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), t, v, k, s, _stream())
+    return out
 
 
 # ------------------------------------------------------------ logit processors

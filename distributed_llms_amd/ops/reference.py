@@ -420,6 +420,34 @@ def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, 
             torch.from_numpy(tl).to(torch.float32).to(dev))
 
 
+# ------------------------------------------------------------------ prompt scoring
+# The contract of csrc/kernels/lm_head_logprobs.hip: the log-probability the LM head gives the token that
+# follows each row, with the logits as the LM-head GEMMs store them and the softmax in float64.
+#   l_ij = bf16(sum_k x_ik w_jk), accumulated in f32 and rounded once;  m_i = max_j l_ij;
+#   lp_i = (l_{i,t_i} - m_i) - ln(sum_j exp(l_ij - m_i))
+#   targets[i] < 0    the row is skipped: lp_i = 0.0, nothing of it is computed
+#   targets[i] >= V   ValueError here, on the host.  The fused kernel reads targets on the device only
+#                     (no host read: graph-capturable); such an id finds no column there and gives -inf
+def lm_head_logprobs(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    """x [T, K], w [V, K], targets [T] int32 -> float32 [T] on x's device."""
+    import numpy as np
+    tg = targets.detach().cpu().numpy().astype(np.int64)
+    v = w.shape[0]
+    if tg.size and tg.max() >= v:
+        raise ValueError(f"lm_head_logprobs: target {int(tg.max())} outside the vocabulary of {v}")
+    out = np.zeros(tg.shape[0], dtype=np.float64)
+    rows = np.flatnonzero(tg >= 0)
+    wf = w.detach().float().cpu()
+    step = max(1, (1 << 24) // max(v, 1))         # bound the [rows, V] temporaries
+    for s in range(0, rows.size, step):
+        r = rows[s:s + step]
+        lg = (x.detach()[torch.from_numpy(r).to(x.device)].float().cpu() @ wf.t()).to(torch.bfloat16)
+        lg = lg.to(torch.float64).numpy()
+        d = lg - lg.max(axis=1, keepdims=True)
+        out[r] = d[np.arange(r.size), tg[r]] - np.log(np.exp(d).sum(axis=1))
+    return torch.from_numpy(out).to(torch.float32).to(x.device)
+
+
 # ------------------------------------------------------------------ logit processors
 # The contract of csrc/kernels/logit_processors.hip, in numpy float32.  Two per-token quantities of
 # a request drive it: in_prompt[t] (t occurs in its prompt) and n_out[t] (how often t occurs in its

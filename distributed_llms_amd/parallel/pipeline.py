@@ -39,7 +39,7 @@ from ..engine.sampler import ids_message_len, sample_step, unpack_ids_message
 from ..engine.scheduler import Scheduler, Step
 from ..engine.logit_state import LogitState
 from ..engine.sequence import (SamplingParams, Sequence, fused_sampler_serves, request_seed, resolve_adapter,
-                               validate_logprobs, validate_processors, validate_sampling)
+                               validate_logprobs, validate_processors, validate_prompt_logprobs, validate_sampling)
 from ..models.lora import adapter_slots
 from ..utils.tracing import get_tracer
 from .comm import STOP, PendingIds, Transport
@@ -141,6 +141,8 @@ class PipelineDriver:
         params = params or SamplingParams()
         if validate_logprobs(params.logprobs) is not None and self.tp is not None:
             raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
+        if validate_prompt_logprobs(params.prompt_logprobs):      # a driver exists only with two stages or more
+            raise ValueError("prompt_logprobs are not supported on a pipeline of more than one stage")
         if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
             raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
         # the last stage samples: stages of one pipeline share a device type and dtype

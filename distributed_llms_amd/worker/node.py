@@ -31,7 +31,7 @@ import torch
 from ..config import EngineConfig, ModelConfig, get_model_config, resolve_device
 from ..models import weights as W
 from ..models.stage import BatchMeta, ModelStage
-from ..network.protocol import (MessageProtocol, pack_ids, pack_result, pack_tensors, unpack_ids,
+from ..network.protocol import (MessageProtocol, pack_ids, pack_prompt_logprobs, pack_result, pack_tensors, unpack_ids,
                                 unpack_tensors)
 
 log = logging.getLogger("dllm.worker")
@@ -555,7 +555,8 @@ class WorkerNode:
                 try:
                     seq = target.add_request(ids, params, request_id=task_id)
                 except ValueError as e:     # refused at admission: this request fails, the loop goes on serving
-                    self.proto.send_message(sock, "ERROR", metadata={"error": str(e), "task_id": task_id})
+                    self.proto.send_message(sock, "ERROR",
+                                            metadata={"error": str(e), "task_id": task_id, "refused": True})
                     continue
                 owners[task_id] = sock
                 if stream:
@@ -582,8 +583,11 @@ class WorkerNode:
                 n_lp = s.params.logprobs
                 if n_lp is not None:      # the values ride in the payload behind the ids; the count here
                     meta["logprobs"] = n_lp
-                self.proto.send_message(sock, "RESULT", payload=pack_result(s.output, s.logprobs, n_lp),
-                                        metadata=meta)
+                payload = pack_result(s.output, s.logprobs, n_lp)
+                if s.prompt_logprobs is not None:      # likewise, behind everything else
+                    meta["prompt_logprobs"] = len(s.prompt_logprobs)
+                    payload += pack_prompt_logprobs(s.prompt_logprobs)
+                self.proto.send_message(sock, "RESULT", payload=payload, metadata=meta)
 
     def _teardown_pipeline(self, send_stop: bool):
         if self.driver is not None and send_stop:

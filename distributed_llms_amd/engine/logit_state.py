@@ -7,7 +7,7 @@ per request that asks (``Sequence.state_row``, handed out by the Scheduler), wor
 count of token t | STATE_BIAS_BIT | STATE_PROMPT_BIT (ops/reference.py), plus the request's bias
 list in small side tensors.  The kernels of csrc/kernels/logit_processors.hip keep a row current
 (``ops.logit_state_update`` for prefill chunks, ``ops.logit_state_count`` for sampled ids) and
-apply it (``ops.apply_logit_processors``); engine/sampler.py ``sample_step`` strings them around a
+apply it (``ops.apply_logit_processors``; the three wrappers: ops/sampling.py); engine/sampler.py ``sample_step`` strings them around a
 step's sampling.
 
 Nothing is allocated until a step carries a processors section: 4 * pitch bytes per row (512 KB at

@@ -26,7 +26,11 @@ def sample(logits: torch.Tensor, temperatures: Optional[Seq[float]] = None, top_
     if temperatures is None or all(t <= 0 for t in temperatures):
         return ops.argmax(logits)
     if seeds is not None:
-        return _sample_seeded(logits, temperatures, top_k, top_p, seeds, positions)
+        par = np.empty((logits.shape[0], 3), dtype=np.int32)     # HostBatch.sampling: inverts sampling_args() exactly
+        par[:, 0] = np.rint(np.asarray(temperatures, dtype=np.float64) * 1e4)
+        par[:, 1] = 0 if top_k is None else np.asarray(top_k)
+        par[:, 2] = 10000 if top_p is None else np.rint(np.asarray(top_p, dtype=np.float64) * 1e4)
+        return _sample_seeded(logits, par, seeds, positions)
     greedy = ops.argmax(logits)
     temps = torch.tensor([max(t, 1e-5) for t in temperatures], device=logits.device, dtype=torch.float32)
     lf = logits.float() / temps.unsqueeze(1)
@@ -81,23 +85,18 @@ def _stage(host: np.ndarray, device) -> torch.Tensor:
     return dev
 
 
-def _sample_seeded(logits, temperatures, top_k, top_p, seeds, positions) -> torch.Tensor:
-    """One staging buffer [params 3B | positions B | seeds 2B] int32, one (pinned, non-blocking on
-    the GPU) copy; the seeds' offset of 4B words keeps them 8-byte aligned."""
+def _sample_seeded(logits, params: np.ndarray, seeds, positions) -> torch.Tensor:
+    """``params`` [B, 3] int32 as in ``HostBatch.sampling``.  One staging buffer [params 3B | positions B |
+    seeds 2B] int32, one (pinned, non-blocking on the GPU) copy; the seeds' offset of 4B words keeps them 8-byte
+    aligned."""
     b = logits.shape[0]
     if positions is None:
         raise ValueError("sample: seeds need positions")
     host = np.empty(6 * b, dtype=np.int32)       # 6 int32 per row: 3 params, 1 position, 2 seed words
-    par = host[:3 * b].reshape(b, 3)
-    par[:, 0] = np.rint(np.asarray(temperatures, dtype=np.float64) * 1e4)
-    par[:, 1] = 0 if top_k is None else np.asarray(top_k)
-    par[:, 2] = 10000 if top_p is None else np.rint(np.asarray(top_p, dtype=np.float64) * 1e4)
+    host[:3 * b] = np.asarray(params).reshape(-1)
     host[3 * b:4 * b] = np.asarray(positions)
     host[4 * b:] = np.asarray(seeds, dtype=np.int32).reshape(-1)
-    if logits.is_cuda:
-        t = _stage(host, logits.device)
-    else:
-        t = torch.from_numpy(host)
+    t = _stage(host, logits.device) if logits.is_cuda else torch.from_numpy(host)
     return ops.sample_rows(logits, t[:3 * b].view(b, 3), t[4 * b:].view(torch.int64), t[3 * b:4 * b])
 
 
@@ -159,25 +158,16 @@ def unpack_prompt_logprobs(msg: np.ndarray, hb) -> Optional[np.ndarray]:
 
 
 def sample_step(logits: torch.Tensor, hb, state=None, eos_id: Optional[int] = None):
-    """``_sample_step`` plus the step's prompt log-probabilities (``hb.prompt_lp``, left by the stage
-    executor) behind its message; a step without a prompt-scoring section answers as before."""
-    ids, msg = _sample_step(logits, hb, state, eos_id)
-    if hb.score_idx is None:
-        return ids, msg
-    if hb.prompt_lp is None:
-        raise ValueError("sample_step: the step has a prompt-scoring section but the stage left no result")
-    return ids, torch.cat([(ids if msg is None else msg).to(torch.int32), hb.prompt_lp.view(torch.int32)])
-
-
-def _sample_step(logits: torch.Tensor, hb, state=None, eos_id: Optional[int] = None):
-    """Sample a step's rows -> (ids [B] int32, message).  ``message`` is None unless a row of the
-    step asked for log-probabilities; then it is the ids message above: one more kernel
-    (``ops.token_logprobs``) over the logits the ids were drawn from.
+    """Sample a step's rows -> (ids [B] int32, message).  ``message`` is None unless a row of the step asked for
+    log-probabilities -- then it is the ids message above: one more kernel (``ops.token_logprobs``) over the logits
+    the ids were drawn from -- or the step has a prompt-scoring section, whose result (``hb.prompt_lp``, left by
+    the stage executor) follows the ids message, or the ids alone.
 
     A step with a processors section (``hb.procs``; ``state``: the caller's LogitState, ``eos_id``
     the id min_tokens bans) first brings the state rows of its prefill chunks up to date, then
     rewrites the asking rows of ``logits`` in place -- what argmax, the sampler and the
-    log-probabilities then see -- and afterwards counts the ids those rows drew."""
+    log-probabilities then see -- and afterwards counts the ids those rows drew.  The int32 ``hb.sampling`` rows
+    reach the seeded kernel as they are; a row draws the token at index ``hb.seq_lens[row]``, its context's end."""
     sec = None
     if hb.procs is not None:
         if state is None:
@@ -189,16 +179,22 @@ def _sample_step(logits: torch.Tensor, hb, state=None, eos_id: Optional[int] = N
             ops.logit_state_update(state, sec["ids"], sec["cu_seqlens"], sec["procs"], sec["bias_cu"],
                                    sec["bias_ids"], sec["bias_vals"])
         ops.apply_logit_processors(logits, state, sec["procs"], sec["seq_lens"], -1 if eos_id is None else eos_id)
-    ids = sample(logits, **hb.sampling_args())
+    if hb.sampling is not None and hb.sample_seeds is not None and (hb.sampling[:, 0] > 0).any():
+        ids = _sample_seeded(logits, hb.sampling, hb.sample_seeds, hb.seq_lens)
+    else:
+        ids = sample(logits, **hb.sampling_args())       # every row greedy (argmax), or no seeds (the torch chain)
     if sec is not None:
-        ids = ids.to(torch.int32)
         ops.logit_state_count(state, ids, sec["procs"])
-    if hb.logprobs is None:
-        return ids, None
-    want = np.ascontiguousarray(hb.logprobs, dtype=np.int32)
-    want_t = _stage(want, logits.device) if logits.is_cuda else torch.from_numpy(want)
-    ids = ids.to(torch.int32)
-    return ids, pack_ids_message(ids, *ops.token_logprobs(logits, ids, want_t, _top_n(hb)))
+    msg = None
+    if hb.logprobs is not None:
+        want = np.ascontiguousarray(hb.logprobs, dtype=np.int32)
+        want_t = _stage(want, logits.device) if logits.is_cuda else torch.from_numpy(want)
+        msg = pack_ids_message(ids, *ops.token_logprobs(logits, ids, want_t, _top_n(hb)))
+    if hb.score_idx is not None:
+        if hb.prompt_lp is None:
+            raise ValueError("sample_step: the step has a prompt-scoring section but the stage left no result")
+        msg = torch.cat([(ids if msg is None else msg).to(torch.int32), hb.prompt_lp.view(torch.int32)])
+    return ids, msg
 
 
 def step_sampling_args(seqs) -> dict:

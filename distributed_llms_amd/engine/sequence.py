@@ -60,7 +60,7 @@ class SamplingParams:
         return SamplingParams(**{k: v for k, v in (d or {}).items() if k in SamplingParams.__dataclass_fields__})
 
 
-MAX_LOGPROBS = 20      # ops.MAX_LOGPROBS: the top slots of the kernel
+MAX_LOGPROBS = 20      # ops/sampling.py MAX_LOGPROBS: the top slots of the kernel
 
 
 def validate_logprobs(value) -> Optional[int]:
@@ -92,7 +92,7 @@ def check_prompt_logprobs_head(weight) -> None:
                          "weight must be a plain bf16 or float tensor")
 
 
-SAMPLE_MAX_VOCAB = 131072      # ops.SAMPLE_MAX_VOCAB: the row the fused sampler holds in registers
+SAMPLE_MAX_VOCAB = 131072      # ops/sampling.py SAMPLE_MAX_VOCAB: the row the fused sampler holds in registers
 
 
 def fused_sampler_serves(device, dtype, kernel_knobs=None) -> bool:

@@ -80,7 +80,7 @@ class Knobs:
     # the LM head while comm kernels may hold CUs (a GPU pipeline stage with RCCL): "sq" (gemm_sq,
     # unaffected by a spinning receive) or "pp" (the nontemporal gemm_pp, faster alone)
     head_beside_comm: str = "sq"
-    # ---- attention (ops/__init__.py)
+    # ---- attention (ops/attention.py)
     attn_target_waves: int = 1024     # decode split-KV: waves to aim for (profiles/attn_decode_sweep.txt)
     prefill_attn: int = 0             # prefill kernel: 0 = auto (9 from prefill_w32_min_q query rows at head_dim 128 -- 7 while comm kernels hold CUs -- else 4); 4 = LDS-shared K/V tiles on 16x16 MFMAs, 7 = the same on 32x32x16 MFMAs with P.V overlapping the softmax, 9 = 7 persistent (one workgroup per CU), 3 = register-tiled (> 32k fallback)
     prefill_w32_min_q: int = 384      # auto: the 32x32 kernel from this many query rows (128 x 256-token prompts: v4 209-215 us, v9 210-212; 96 x 384: 267-272 vs 260-262; profiles/round6_attention.md)
@@ -107,7 +107,7 @@ class Knobs:
     # seeded sampling (temperature / top-k / top-p / Philox draw) in one HIP kernel behind the LM
     # head (csrc/kernels/sampler.hip; cost against ops.argmax and the torch chain of
     # engine/sampler.py: profiles/sampler.md).  False: seeded rows take ops/reference.py
-    # sample_rows, the same contract in numpy on the host
+    # sample_rows, the same contract in numpy on the host; what else follows it: ops/sampling.py route
     fused_sampler: bool = True
     # RCCL transport comm streams (send / recv / ring / ids copy): "pool" (torch pool streams) or
     # "priority" (one native high-priority stream per role: a queue of its own, but a spinning

@@ -34,11 +34,17 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _ck(t: torch.Tensor, name: str, dtype=torch.bfloat16):
+def _ck(t: torch.Tensor, name: str, dtype=torch.bfloat16, shape=None, device=None):
+    """``t`` is a contiguous ``dtype`` tensor -- of ``shape`` (an extent of None: any) and on ``device``, if given."""
     if t.dtype != dtype:
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
     if not t.is_contiguous():
         raise ValueError(f"{name}: must be contiguous")
+    if shape is not None and t.shape != shape and (t.dim() != len(shape) or
+                                                   any(s is not None and s != d for s, d in zip(shape, t.shape))):
+        raise ValueError(f"{name}: must be {list(shape)} (None: any extent), got {list(t.shape)}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: must be on {device}, is on {t.device}")
 
 
 def _gpu(t: torch.Tensor) -> bool:
@@ -217,257 +223,9 @@ from .attention import (MAX_DECODE_SPLITS, PF_MAX_CHUNKS, PF_SPLIT_MAX_PLAIN_WGS
                         prefill_split_eligible, prefill_split_plan, rope_cache_append)
 
 
-# ------------------------------------------------------------- K10
-def argmax(logits: torch.Tensor) -> torch.Tensor:
-    if not _gpu(logits):
-        return ref.argmax(logits)
-    if logits.dtype != torch.bfloat16:
-        return logits.argmax(-1).to(torch.int32)
-    if logits.stride(-1) != 1:
-        raise ValueError("argmax: last dim must be contiguous")
-    rows, v = logits.shape
-    out = torch.empty(rows, dtype=torch.int32, device=logits.device)
-    _ext.kernels().argmax(out.data_ptr(), logits.data_ptr(), rows, v, logits.stride(0), _stream())
-    return out
-
-
-SAMPLE_MAX_VOCAB = 131072      # csrc/kernels/sampler.hip: 16 groups of 8 entries per thread, 1024 threads
-_host_sampler_warned = False
-
-
-def _warn_host_sampler(logits: torch.Tensor, op: str = "sample_rows") -> None:
-    """Once per process: GPU logits are about to be sampled by the host reference."""
-    global _host_sampler_warned
-    if not _host_sampler_warned:
-        _host_sampler_warned = True
-        import logging
-        logging.getLogger("dllm.ops").warning(
-            "%s: %s logits on %s take the host reference (knobs.fused_sampler=%s): the [B, V] logits are "
-            "copied to the host every step, which synchronises the device and cannot be graph-captured",
-            op, logits.dtype, logits.device, knobs.K.fused_sampler)
-
-
-def sample_rows(logits: torch.Tensor, params: torch.Tensor, seeds: torch.Tensor, pos: torch.Tensor,
-                uniforms: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Seeded temperature / top-k / top-p sampling, one id per row (contract: ops/reference.py).
-
-    logits [B, V]; params [B, 3] int32 (temperature * 1e4, top_k, top_p * 1e4); seeds [B] int64
-    (the 64-bit seed's bit pattern); pos [B] int32 (index of the token being drawn); uniforms [B]
-    float32 or None (test hook: replaces the Philox draw).  Every per-row value is read on the
-    device: no host synchronisation, graph-capturable.  bf16 CUDA logits with a contiguous last dim
-    (at most SAMPLE_MAX_VOCAB entries) take the HIP kernel; anything else, and everything with
-    ``knobs.fused_sampler`` off, the reference -- numpy on the host, so GPU logits then cost a
-    device-to-host copy and a synchronisation per step (logged once)."""
-    if not (_gpu(logits) and logits.dtype == torch.bfloat16 and logits.stride(-1) == 1 and knobs.K.fused_sampler):
-        if _gpu(logits):
-            _warn_host_sampler(logits)
-        return ref.sample_rows(logits, params, seeds, pos, uniforms)
-    rows, v = logits.shape
-    if v > SAMPLE_MAX_VOCAB:
-        raise ValueError(f"sample_rows: vocab {v} exceeds the kernel's register-resident row of {SAMPLE_MAX_VOCAB}")
-    dev = logits.device
-    _ck(params, "sample_rows.params", torch.int32)
-    _ck(seeds, "sample_rows.seeds", torch.int64)
-    _ck(pos, "sample_rows.pos", torch.int32)
-    if params.shape != (rows, 3) or seeds.shape != (rows,) or pos.shape != (rows,):
-        raise ValueError(f"sample_rows: params / seeds / pos must be [{rows}, 3] / [{rows}] / [{rows}]")
-    if uniforms is not None:
-        _ck(uniforms, "sample_rows.uniforms", torch.float32)
-        if uniforms.shape != (rows,):
-            raise ValueError(f"sample_rows: uniforms must be [{rows}]")
-    if any(t.device != dev for t in (params, seeds, pos) + (() if uniforms is None else (uniforms,))):
-        raise ValueError("sample_rows: params, seeds, pos and uniforms must be on the logits' device")
-    out = torch.empty(rows, dtype=torch.int32, device=dev)
-    _ext.kernels().sample_rows(out.data_ptr(), logits.data_ptr(), rows, v, logits.stride(0), params.data_ptr(),
-                               seeds.data_ptr(), pos.data_ptr(), 0 if uniforms is None else uniforms.data_ptr(),
-                               _stream())
-    return out
-
-
-MAX_LOGPROBS = ref.MAX_LOGPROBS     # csrc/kernels/launchers.h kMaxLogprobs
-
-
-def token_logprobs(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, n_max: int):
-    """Log-probabilities of the model's distribution (contract: ops/reference.py token_logprobs).
-
-    logits [B, V]; ids [B] int32 (the token each row chose); want [B] int32 (-1: the row is
-    skipped, else how many of the most likely entries to report, at most ``n_max`` <=
-    MAX_LOGPROBS) -> (chosen [B] float32, top_ids [B, n_max] int32, top_lp [B, n_max] float32).
-    Every per-row value is read on the device.  bf16 CUDA logits with a contiguous last dim of at
-    most SAMPLE_MAX_VOCAB entries take the HIP kernel; anything else, and everything with
-    ``knobs.fused_sampler`` off, the host reference (GPU logits: logged once, as sample_rows)."""
-    n_max = int(n_max)
-    if not 0 <= n_max <= MAX_LOGPROBS:
-        raise ValueError(f"token_logprobs: n_max must be in [0, {MAX_LOGPROBS}], got {n_max}")
-    if logits.dim() != 2:
-        raise ValueError("token_logprobs: logits must be [B, V]")
-    rows, v = logits.shape
-    _ck(ids, "token_logprobs.ids", torch.int32)
-    _ck(want, "token_logprobs.want", torch.int32)
-    if ids.shape != (rows,) or want.shape != (rows,):
-        raise ValueError(f"token_logprobs: ids / want must be [{rows}] / [{rows}]")
-    if ids.device != logits.device or want.device != logits.device:
-        raise ValueError("token_logprobs: ids and want must be on the logits' device")
-    if not (_gpu(logits) and logits.dtype == torch.bfloat16 and logits.stride(-1) == 1 and knobs.K.fused_sampler
-            and v <= SAMPLE_MAX_VOCAB):
-        if _gpu(logits):
-            _warn_host_sampler(logits, "token_logprobs")
-        return ref.token_logprobs(logits, ids, want, n_max)
-    dev = logits.device
-    chosen = torch.empty(rows, dtype=torch.float32, device=dev)
-    top_ids = torch.empty(rows, n_max, dtype=torch.int32, device=dev)
-    top_lp = torch.empty(rows, n_max, dtype=torch.float32, device=dev)
-    _ext.kernels().token_logprobs(chosen.data_ptr(), top_ids.data_ptr(), top_lp.data_ptr(), logits.data_ptr(), rows, v,
-                                  logits.stride(0), ids.data_ptr(), want.data_ptr(), n_max, _stream())
-    return chosen, top_ids, top_lp
-
-
-def lm_head_ranges(t: int, v: int, cus: int = 256, comm_cus: Optional[int] = None) -> int:
-    """Vocabulary ranges S of the fused LM-head log-likelihood kernel: its grid is ceil(T / 256) row tiles x S,
-    about one workgroup per CU that no comm kernel may hold (ops/gemm.py), a range at least one 256-column tile."""
-    comm = gemm.comm_cus() if comm_cus is None else comm_cus
-    return max(1, min(-(-v // 256), (cus - comm) // -(-t // 256)))
-
-
-def lm_head_logprobs(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, ranges: int = 0) -> torch.Tensor:
-    """Log-probability the LM head gives each row's target token (contract: ops/reference.py lm_head_logprobs):
-    log_softmax(bf16(x w^T))[i, targets[i]] with linear, log-softmax and gather fused -- no [T, V] logits exist.
-
-    x [T, K]; w [V, K]; targets [T] int32 (negative: the row is skipped and gets 0.0) -> float32 [T].  bf16 CUDA
-    operands with K % 64 == 0 take the HIP kernel (csrc/kernels/lm_head_logprobs.hip: any T and V, partial triples
-    in the per-stream GEMM workspace, every value read on the device, graph-capturable, the same bits on every
-    launch); CPU tensors, other dtypes and everything with ``knobs.fused_sampler`` off take the reference, which
-    also refuses a target >= V.  The kernel cannot (it reads targets on the device only) and gives such a row -inf:
-    a caller that does not know its targets are below V checks them on the host first (the engine's are prompt
-    tokens, validated against the vocabulary by the embedding path).
-    ``ranges``: the kernel's vocabulary ranges (0: :func:`lm_head_ranges`)."""
-    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
-        raise ValueError(f"lm_head_logprobs: x [T, K] and w [V, K], got {tuple(x.shape)} and {tuple(w.shape)}")
-    t, k = x.shape
-    v = w.shape[0]
-    _ck(targets, "lm_head_logprobs.targets", torch.int32)
-    if targets.shape != (t,):
-        raise ValueError(f"lm_head_logprobs: targets must be [{t}]")
-    if w.device != x.device or targets.device != x.device:
-        raise ValueError("lm_head_logprobs: w and targets must be on x's device")
-    if t == 0:
-        return torch.empty(0, dtype=torch.float32, device=x.device)
-    if not (_gpu(x) and x.dtype == w.dtype == torch.bfloat16 and knobs.K.fused_sampler):
-        return ref.lm_head_logprobs(x, w, targets)
-    _ck(x, "lm_head_logprobs.x")
-    _ck(w, "lm_head_logprobs.w")
-    if k % 64 or k < 64 or t * k * 2 >= 1 << 32 or v * k * 2 >= 1 << 32:
-        raise ValueError("lm_head_logprobs: the kernel needs K % 64 == 0 and operands below 4 GiB")
-    s = int(ranges) or lm_head_ranges(t, v, gemm._cus(x.device))
-    if not 1 <= s <= -(-v // 256):
-        raise ValueError(f"lm_head_logprobs: ranges must be in [1, {-(-v // 256)}], got {s}")
-    ws = gemm._workspace(x.device)
-    need = t * _ext.kernels().LM_HEAD_WAVES * s * 3       # (m, l, target logit) per row, range and wave
-    if need > ws.numel():
-        raise ValueError(f"lm_head_logprobs: {t} rows x {s} ranges need {need} workspace floats, "
-                         f"the pool holds {ws.numel()}; score the rows in slices")
-    out = torch.empty(t, dtype=torch.float32, device=x.device)
-    _ext.kernels().lm_head_logprobs(out.data_ptr(), x.data_ptr(), w.data_ptr(), targets.data_ptr(), ws.data_ptr(),
-                                    ws.numel(), t, v, k, s, _stream())
-    return out
-
-
-# ------------------------------------------------------------ logit processors
-# Penalties, logit_bias and the min_tokens EOS ban (contract: ops/reference.py).  ``ls`` is an
-# engine.logit_state.LogitState (or anything with its tensors): state [rows, pitch] int32, bias_n
-# [rows] int32, bias_ids [rows, P] int32, bias_vals [rows, P] float32, and ``vocab``.
-def _fused_processors(logits_like: torch.Tensor, vocab: int) -> bool:
-    return _gpu(logits_like) and knobs.K.fused_sampler and vocab <= SAMPLE_MAX_VOCAB
-
-
-def _ck_state(ls, op: str, procs: torch.Tensor, rows: int):
-    _ck(ls.state, f"{op}.state", torch.int32)
-    _ck(procs, f"{op}.procs", torch.int32)
-    if procs.shape != (rows, ref.PROC_WORDS):
-        raise ValueError(f"{op}: procs must be [{rows}, {ref.PROC_WORDS}]")
-    if ls.state.dim() != 2 or ls.state.shape[1] % 8 or ls.state.shape[1] < ls.vocab:
-        raise ValueError(f"{op}: state must be [rows, pitch], pitch a multiple of 8 covering the vocabulary")
-    _ck(ls.bias_n, f"{op}.bias_n", torch.int32)
-    _ck(ls.bias_ids, f"{op}.bias_ids", torch.int32)
-    _ck(ls.bias_vals, f"{op}.bias_vals", torch.float32)
-    n = ls.state.shape[0]
-    if ls.bias_n.shape != (n,) or ls.bias_ids.dim() != 2 or ls.bias_ids.shape[0] != n \
-            or ls.bias_vals.shape != ls.bias_ids.shape:
-        raise ValueError(f"{op}: bias_n / bias_ids / bias_vals must be [{n}] / [{n}, P] / [{n}, P]")
-    if any(t.device != ls.state.device for t in (procs, ls.bias_n, ls.bias_ids, ls.bias_vals)):
-        raise ValueError(f"{op}: procs and the bias tensors must be on the state's device")
-
-
-def logit_state_update(ls, ids: torch.Tensor, cu_seqlens: torch.Tensor, procs: torch.Tensor,
-                       step_bias_cu: torch.Tensor, step_bias_ids: torch.Tensor, step_bias_vals: torch.Tensor) -> None:
-    """A step's prefill chunks enter the state: ids [T] int32, cu_seqlens [B + 1] int32, procs
-    [B, PROC_WORDS] int32 (rows with PROC_UPDATE and a state row take part; PROC_START is the
-    position of the chunk's first token), step_bias_* the bias lists of the step (cu [B + 1], ids
-    and float32 values [n]) that chunks starting at position 0 install."""
-    rows = procs.shape[0]
-    _ck_state(ls, "logit_state_update", procs, rows)
-    _ck(ids, "logit_state_update.ids", torch.int32)
-    _ck(cu_seqlens, "logit_state_update.cu_seqlens", torch.int32)
-    _ck(step_bias_cu, "logit_state_update.step_bias_cu", torch.int32)
-    _ck(step_bias_ids, "logit_state_update.step_bias_ids", torch.int32)
-    _ck(step_bias_vals, "logit_state_update.step_bias_vals", torch.float32)
-    if cu_seqlens.shape != (rows + 1,) or step_bias_cu.shape != (rows + 1,) \
-            or step_bias_ids.shape != step_bias_vals.shape or step_bias_ids.dim() != 1:
-        raise ValueError("logit_state_update: cu_seqlens / step_bias_cu must be [B + 1], the bias lists [n]")
-    if any(t.device != ls.state.device for t in (ids, cu_seqlens, step_bias_cu, step_bias_ids, step_bias_vals)):
-        raise ValueError("logit_state_update: every tensor must be on the state's device")
-    if not _fused_processors(ls.state, ls.vocab):
-        return ref.logit_state_update(ls.state, ls.vocab, ids, cu_seqlens, procs, ls.bias_n, ls.bias_ids,
-                                      ls.bias_vals, step_bias_cu, step_bias_ids, step_bias_vals)
-    _ext.kernels().logit_state_update(ls.state.data_ptr(), ls.state.shape[1], ls.state.shape[0], ls.vocab,
-                                      ids.data_ptr(), cu_seqlens.data_ptr(), procs.data_ptr(), rows,
-                                      ls.bias_n.data_ptr(), ls.bias_ids.data_ptr(), ls.bias_vals.data_ptr(),
-                                      ls.bias_ids.shape[1], step_bias_cu.data_ptr(), step_bias_ids.data_ptr(),
-                                      step_bias_vals.data_ptr(), _stream())
-
-
-def apply_logit_processors(logits: torch.Tensor, ls, procs: torch.Tensor, seq_lens: torch.Tensor,
-                           eos_id: int) -> torch.Tensor:
-    """The processors on ``logits`` [B, V], in place, for the rows with PROC_SAMPLE and a state row;
-    every other row is neither read nor written.  seq_lens [B] int32: a row draws output token
-    number seq_lens - prompt_len, and ``eos_id`` (-1: none) is banned while that is < min_tokens.
-    bf16 CUDA logits with a contiguous last dim of at most SAMPLE_MAX_VOCAB entries take the HIP
-    kernel (with ``knobs.fused_sampler`` on); anything else the reference."""
-    if logits.dim() != 2 or logits.shape[1] != ls.vocab:
-        raise ValueError(f"apply_logit_processors: logits must be [B, {ls.vocab}]")
-    rows, v = logits.shape
-    _ck_state(ls, "apply_logit_processors", procs, rows)
-    _ck(seq_lens, "apply_logit_processors.seq_lens", torch.int32)
-    if seq_lens.shape != (rows,) or seq_lens.device != logits.device or ls.state.device != logits.device:
-        raise ValueError("apply_logit_processors: seq_lens must be [B]; everything on the logits' device")
-    eos_id = -1 if eos_id is None else int(eos_id)
-    if not -1 <= eos_id < v:
-        raise ValueError(f"apply_logit_processors: eos id {eos_id} outside the vocabulary")
-    if not (_fused_processors(logits, v) and logits.dtype == torch.bfloat16 and logits.stride(-1) == 1
-            and (rows <= 1 or logits.stride(0) >= v)):
-        if _gpu(logits):
-            _warn_host_sampler(logits, "apply_logit_processors")
-        ref.apply_logit_processors(logits, ls.state, procs, seq_lens, eos_id, ls.bias_n, ls.bias_ids, ls.bias_vals)
-        return logits
-    _ext.kernels().apply_logit_processors(logits.data_ptr(), rows, v, max(logits.stride(0), v), ls.state.data_ptr(),
-                                          ls.state.shape[1], ls.state.shape[0], procs.data_ptr(), seq_lens.data_ptr(),
-                                          eos_id, ls.bias_n.data_ptr(), ls.bias_ids.data_ptr(),
-                                          ls.bias_vals.data_ptr(), ls.bias_ids.shape[1], _stream())
-    return logits
-
-
-def logit_state_count(ls, ids: torch.Tensor, procs: torch.Tensor) -> None:
-    """After sampling: ids [B] int32, the id each row drew; rows with PROC_SAMPLE and a state row
-    add one to that id's count."""
-    rows = procs.shape[0]
-    _ck_state(ls, "logit_state_count", procs, rows)
-    _ck(ids, "logit_state_count.ids", torch.int32)
-    if ids.shape != (rows,) or ids.device != ls.state.device:
-        raise ValueError(f"logit_state_count: ids must be [{rows}] on the state's device")
-    if not _fused_processors(ls.state, ls.vocab):
-        return ref.logit_state_count(ls.state, ls.vocab, ids, procs)
-    _ext.kernels().logit_state_count(ls.state.data_ptr(), ls.state.shape[1], ls.state.shape[0], ls.vocab,
-                                     ids.data_ptr(), procs.data_ptr(), rows, _stream())
+# ------------------------------------- K10 and the sampling stage: ops/sampling.py
+from .sampling import (MAX_LOGPROBS, SAMPLE_MAX_VOCAB, apply_logit_processors, argmax, lm_head_logprobs,  # noqa: E402,F401
+                       lm_head_ranges, logit_state_count, logit_state_update, sample_rows, token_logprobs)
 
 
 # ------------------------------------------------------------ K11/K12

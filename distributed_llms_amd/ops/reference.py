@@ -249,7 +249,7 @@ def argmax(logits: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ seeded sampling
-# The contract of csrc/kernels/sampler.hip, in numpy with float64 masses.  Per row: int32 params
+# The contract of csrc/kernels/sampler.hip (host side: ops/sampling.py), in numpy with float64 masses.  Per row: int32 params
 # (temp_e4, top_k, top_p_e4), a 64-bit seed and pos, the index of the token being drawn.
 #   temp_e4 <= 0  the argmax (first index on ties; NaN counts as -inf; an all -inf row gives 0)
 #   otherwise     x = l / T with T = temp_e4 * 1e-4, w = exp(x - x_max)

@@ -148,6 +148,29 @@ def test_knob_off_takes_the_reference(cuda):
     assert got.device.type == "cuda" and got.cpu().tolist() == want.tolist()
 
 
+def test_sample_step_hands_the_batch_rows_to_the_kernel(cuda):
+    """A step's int32 ``HostBatch.sampling`` rows, seeds and ``seq_lens`` reach the kernel unchanged: sample_step
+    draws what ops.sample_rows draws from the same int32 tensors, and what the reference draws.  V = 264 is 33 groups
+    of 8 (a ragged iteration of the 1024-thread workgroup); a greedy row, T = 1e-4 with k = 1, T = 0.7 with p = 0.9999."""
+    from distributed_llms_amd.engine.batch import HostBatch
+    from distributed_llms_amd.engine.sampler import sample_step
+    from distributed_llms_amd.engine.sequence import split_seed
+    b, v = 3, 264
+    logits = (torch.randn(b, v, generator=torch.Generator().manual_seed(264)) * 3).to(torch.bfloat16)
+    samp = np.array([[0, 0, 10000], [1, 1, 10000], [7000, 0, 9999]], dtype=np.int32)
+    seeds = np.array([split_seed(s) for s in (11, 2 ** 63 + 5, 2 ** 64 - 1)], dtype=np.int32)
+    seq_lens = np.array([5, 77, 1234], dtype=np.int32)
+    i32 = lambda n: np.arange(n, dtype=np.int32)
+    hb = HostBatch(False, i32(b), i32(b), i32(b), seq_lens, i32(b + 1), i32(2 * b).reshape(b, 2), i32(b), 1, 1234,
+                   sampling=samp, sample_seeds=seeds)
+    par, s64, pos = torch.from_numpy(samp), torch.from_numpy(seeds).view(torch.int64).reshape(b), torch.from_numpy(seq_lens)
+    ids, msg = sample_step(logits.to(cuda), hb)
+    direct = ops.sample_rows(logits.to(cuda), par.to(cuda), s64.to(cuda), pos.to(cuda))
+    assert msg is None and ids.dtype == torch.int32 and ids.device.type == "cuda"
+    assert ids.cpu().tolist() == direct.cpu().tolist() == ref.sample_rows(logits, par, s64, pos).tolist()
+    assert ids[:2].cpu().tolist() == logits[:2].float().argmax(-1).tolist()
+
+
 def test_distribution(cuda):
     """V = 37, T = 1.3, k = 12, p = 0.9, pos = 0..65535 under one seed: no draw outside the kept set
     and a chi-square against the reference's exact kept probabilities under the 99.9 % point."""

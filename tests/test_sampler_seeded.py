@@ -132,6 +132,48 @@ def test_sampler_with_seeds_takes_the_reference_on_the_cpu():
     assert again.tolist() == ids.tolist()
 
 
+def test_float_sampling_args_convert_back_to_the_int32_rows(monkeypatch):
+    """A step hands its int32 ``HostBatch.sampling`` rows to ops.sample_rows as they are, ``sample()`` converts the
+    float lists of ``sampling_args()`` back: both hand over the same int32, for every temperature up to 20 and
+    every top_p up to 1 in steps of 1e-4 (rint(float64(x / 1e4) * 1e4) == x)."""
+    from distributed_llms_amd import ops
+    from distributed_llms_amd.engine.sampler import sample_step
+    n = 200001
+    samp = np.stack([np.arange(n), np.arange(n) % 97, np.arange(n) % 10001], axis=1).astype(np.int32)
+    hb = _hb(np.zeros((n, 2), dtype=np.int32), samp, b=n)
+    seen = []
+    monkeypatch.setattr(ops, "sample_rows", lambda logits, par, seeds, pos: seen.append((par, pos)) or pos)
+    logits = torch.zeros(n, 2)
+    sample(logits, **hb.sampling_args())
+    sample_step(logits, hb)
+    for par, pos in seen:
+        assert par.dtype == torch.int32 and np.array_equal(par.numpy(), samp) and np.array_equal(pos.numpy(), hb.seq_lens)
+    assert len(seen) == 2
+    sample(logits[:2], [0.7, 0.0], seeds=np.zeros((2, 2), dtype=np.int32), positions=[0, 1])
+    assert seen[2][0].tolist() == [[7000, 0, 10000], [0, 0, 10000]]
+
+
+def test_sample_step_and_sample_draw_the_same_ids_on_the_cpu():
+    """The step's path (int32 rows straight from the batch) against sample() on the batch's float arguments and
+    against the reference; a step whose rows are all greedy, and one without seeds, take argmax / the torch chain."""
+    from distributed_llms_amd.engine.sampler import sample_step
+    g = torch.Generator().manual_seed(5)
+    logits = torch.randn(3, 264, generator=g) * 2
+    samp = np.array([[0, 0, 10000], [1, 1, 10000], [7000, 0, 9999]], dtype=np.int32)
+    seeds = np.array([split_seed(s) for s in (11, 2 ** 63 + 5, 2 ** 64 - 1)], dtype=np.int32)
+    hb = _hb(seeds, samp)
+    ids, msg = sample_step(logits, hb)
+    want = ref.sample_rows(logits, torch.from_numpy(samp), torch.from_numpy(seeds.copy()).view(torch.int64).reshape(3),
+                           torch.from_numpy(hb.seq_lens))
+    assert msg is None and ids.dtype == torch.int32 and ids.tolist() == want.tolist()
+    assert ids.tolist() == sample(logits, **hb.sampling_args()).tolist()
+    assert ids[:2].tolist() == logits[:2].argmax(-1).tolist()
+    greedy = _hb(seeds, np.array([[0, 5, 9000]] * 3, dtype=np.int32))
+    assert sample_step(logits, greedy)[0].tolist() == logits.argmax(-1).tolist()
+    unseeded = _hb(None, np.array([[10000, 1, 10000]] * 3, dtype=np.int32))
+    assert sample_step(logits, unseeded)[0].tolist() == logits.argmax(-1).tolist()      # top_k = 1
+
+
 # ------------------------------------------------------------------ tolerance of the GPU test, measured here
 def test_measured_float32_gap_and_the_widened_cap():
     """sampler_cases.MEASURED_GAP is the float32-vs-float64 mass gap of these very inputs, and the

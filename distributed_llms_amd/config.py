@@ -187,6 +187,21 @@ QWEN_TP_REFUSAL = ("tensor parallelism (tp > 1) is not supported for models with
                    "(Qwen2 / Qwen3): the bias shard is not built")
 QWEN_FP8_REFUSAL = ('quant="fp8" is not supported for models with a qkv bias or a q/k norm (Qwen2 / Qwen3)')
 
+
+
+def check_int4(cfg: ModelConfig, tp: int = 1) -> None:
+    """What quant="int4" (ops/int4.py) does not serve: none of it is wired or tested (ValueError)."""
+    if cfg.arch != "llama" or cfg.is_moe:
+        raise ValueError(f'quant="int4" serves dense Llama-architecture models only (arch {cfg.arch!r}, '
+                         f'{cfg.num_experts} experts)')
+    if cfg.attn_bias or cfg.qk_norm:
+        raise ValueError('quant="int4" is not supported for models with a qkv bias or a q/k norm (Qwen2 / Qwen3)')
+    if tp > 1:
+        raise ValueError('quant="int4" is not supported with tensor parallelism (tp > 1)')
+    if os.environ.get("DLLM_PP_FINE", "0") == "1":
+        raise ValueError('quant="int4" is not supported with sub-layer pipeline cuts (DLLM_PP_FINE=1)')
+
+
 _LLAMA3_ROPE = {"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0,
                 "high_freq_factor": 4.0, "original_max_position_embeddings": 8192}
 
@@ -322,7 +337,7 @@ class EngineConfig:
     # engine/scheduler.py).  Not with tensor parallelism (tp > 1)
     enable_prefix_caching: bool = False
     use_graphs: bool = True            # HIP-graph capture of the decode step
-    quant: str = "none"                # "fp8": W8A8 e4m3 dense projections (ops/quant.py)
+    quant: str = "none"                # "fp8": W8A8 e4m3 dense projections (ops/quant.py); "int4": W4A16 (ops/int4.py)
     # pipeline activation transport between GPU stages: "auto" (= "rccl" on GPUs), "rccl" (native
     # RCCL p2p, one communicator per edge, static rings), "torch" (torch.distributed's RCCL group),
     # "ipc" (HIP-IPC peer writes); CPU stages always use torch.distributed (gloo)
@@ -355,8 +370,8 @@ class EngineConfig:
             raise ValueError("num_workers and dp_replicas must be >= 1")
         if self.kv_block_size not in (16, 32, 64):
             raise ValueError("kv_block_size must be 16, 32 or 64")
-        if self.quant not in ("none", "fp8"):
-            raise ValueError(f"quant {self.quant!r} (none, fp8)")
+        if self.quant not in ("none", "fp8", "int4"):
+            raise ValueError(f"quant {self.quant!r} (none, fp8, int4)")
         if self.transport not in ("auto", "rccl", "torch", "ipc"):
             raise ValueError(f"transport {self.transport!r} (auto, rccl, torch, ipc)")
         if self.comm_timeout_s <= 0:
@@ -376,6 +391,8 @@ class EngineConfig:
             raise ValueError(f"{self.num_workers} stages > {cfg.num_layers} layers")
         if self.quant == "fp8" and (cfg.attn_bias or cfg.qk_norm):
             raise ValueError(QWEN_FP8_REFUSAL)
+        if self.quant == "int4":
+            check_int4(cfg)
         if self.lora_modules:
             if not isinstance(self.lora_modules, dict):
                 raise ValueError("lora_modules must map adapter names to sources")
@@ -389,6 +406,8 @@ class EngineConfig:
             raise ValueError("prefix caching is not supported with tensor parallelism (tp > 1)")
         if tp > 1 and self.lora_modules:
             raise ValueError("LoRA adapters are not supported with tensor parallelism (tp > 1)")
+        if self.quant == "int4":
+            check_int4(self.model_config(), tp)
         if tp > 1:
             cfg = self.model_config()
             if cfg.attn_bias or cfg.qk_norm:

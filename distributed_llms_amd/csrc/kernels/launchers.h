@@ -82,6 +82,12 @@ void lm_head_logprobs(uintptr_t out, uintptr_t x, uintptr_t w, uintptr_t targets
                       int V, int K, int S, uintptr_t stream);
 int gemm_sq(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats, int M, int N, int K, int splits,
             int mode, int variant, uintptr_t stream);
+// gemm_w4.hip: c [M, N] bf16 = x [M, K] bf16 . wd^T with int4 weights wp (fragment-packed, N K / 2 bytes) and bf16
+// group scales [N / 16, K / 128, 16]; N % 128 == 0, K % 128 == 0.  ws: f32 [S, M, N] partials of the S K slices
+// (returned; 1: none).  dequant_w4: the same weight to bf16 [N, K]
+int gemm_w4a16(uintptr_t c, uintptr_t x, uintptr_t wp, uintptr_t scale, uintptr_t ws, long ws_floats, int M, int N,
+               int K, int splits, uintptr_t stream);
+void dequant_w4(uintptr_t out, uintptr_t wp, uintptr_t scale, int N, int K, uintptr_t stream);
 
 void moe_route(uintptr_t logits, int T, int E, int k, uintptr_t topk_w, uintptr_t topk_ids, uintptr_t counts,
                uintptr_t offsets, uintptr_t sorted_tok, uintptr_t inv, uintptr_t stream);

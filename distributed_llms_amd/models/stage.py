@@ -319,11 +319,19 @@ class ModelStage:
     def quantize(self, mode: str) -> "ModelStage":
         """``"fp8"``: the dense projections (qkv, o, gate|up, down) and MoE expert stacks become
         W8A8 e4m3 weights (ops/quant.py); embeddings, norms, router, LM head and the KV cache stay
-        in ``dtype``."""
+        in ``dtype``.  ``"int4"``: the dense projections become W4A16 weights (ops/int4.py), dense Llama only."""
         if mode in ("", "none", None):
             return self
+        if mode == "int4":
+            # W4A16 group-wise codes (ops/int4.py); a stage none of whose projections it takes is refused
+            from ..config import check_int4
+            from ..ops import int4
+            check_int4(self.cfg, self.tp.size)
+            if not int4.quantize_layers(self.layers):
+                raise ValueError('quant="int4" converted no weight of this stage (N and K multiples of 128)')
+            return self
         if mode != "fp8":
-            raise ValueError(f"unknown quantization {mode!r} (none, fp8)")
+            raise ValueError(f"unknown quantization {mode!r} (none, fp8, int4)")
         if self.cfg.attn_bias or self.cfg.qk_norm:
             raise ValueError(QWEN_FP8_REFUSAL)
         from ..ops import quant

@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import _ext, knobs
-from . import gemm, lora, quant
+from . import gemm, int4, lora, quant
 from . import reference as ref
 
 __all__ = [
@@ -169,11 +169,16 @@ def gelu_tanh(x):
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, defer: bool = False):
     """y = x @ w^T (+bias). w is [N, K].  ``defer`` (GPU): the result may come back as a
     :class:`gemm.SplitKPartial` for ``fused_add_rms_norm`` to reduce (or ``materialize()``).
-    ``w`` may be a :class:`quant.Fp8Weight` (W8A8 e4m3 GEMM, no bias)."""
+    ``w`` may be a :class:`quant.Fp8Weight` (W8A8 e4m3 GEMM, no bias) or an :class:`int4.Int4Weight` (W4A16, no
+    bias, always a dense result)."""
     if isinstance(w, quant.Fp8Weight):
         if bias is not None:
             raise ValueError("linear: fp8 weights take no bias")
         return quant.linear_fp8(x, w, defer=defer)
+    if isinstance(w, int4.Int4Weight):
+        if bias is not None:
+            raise ValueError("linear: int4 weights take no bias")
+        return int4.linear_int4(x, w, defer=defer)
     if not _gpu(x):
         return ref.linear(x, w, bias)
     return gemm.linear(x, w, bias, defer=defer)
@@ -183,6 +188,8 @@ def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
     """silu(x @ Wg^T) * (x @ Wu^T), W = [Wg; Wu]; fused into the GEMM epilogue on the GPU (decode)."""
     if isinstance(w_gate_up, quant.Fp8Weight):
         return quant.linear_fp8(x, w_gate_up, swiglu=True)
+    if isinstance(w_gate_up, int4.Int4Weight):
+        return silu_mul(int4.linear_int4(x, w_gate_up))
     if _gpu(x):
         y = gemm.linear_swiglu(x, w_gate_up)
         if y is not None:                    # None: gemm.route found no fused kernel (GemmRoute.unfused)

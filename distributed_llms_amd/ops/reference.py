@@ -448,6 +448,38 @@ def lm_head_logprobs(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor) ->
     return torch.from_numpy(out).to(torch.float32).to(x.device)
 
 
+# ------------------------------------------------------------------ int4 weights (W4A16)
+# The contract of csrc/kernels/gemm_w4.hip and ops/int4.py.  A weight W is [N, K] with N % 128 == 0 and
+# K % 128 == 0; a quantization group is 128 consecutive k of one row.
+#   quantizer (f32):  s[n, g] = bf16_rne(absmax_g / 7), an all-zero group gets s = 1;
+#                     u[n, k] = clamp(rne(W[n, k] / s[n, k / 128]), -8, 7) + 8, a code in 0..15
+#   dequantized:      wd[n, k] = f32(u[n, k] - 8) * f32(s[n, k / 128])     (exact in f32)
+#   op:               y[m, n] = dtype_rne(sum_k f32(x[m, k]) * wd[n, k]), accumulated in f32 in any order, rounded
+#                     once; no bias.  From ops/int4.py's cutover M on the GPU, wd is rounded to bf16 once before
+#                     the product (the dequant route).  SwiGLU is silu_mul on the dense [M, 2I] result
+W4_GROUP = 128
+
+
+def quantize_w4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[N, K] float weight -> (codes u [N, K] uint8 in 0..15, scales s [N, K / 128] bf16)."""
+    n, k = w.shape
+    wf = w.float().view(n, k // W4_GROUP, W4_GROUP)
+    amax = wf.abs().amax(dim=2)
+    # a tensor divisor: torch divides a GPU tensor by a Python scalar as a multiply by its reciprocal
+    s = torch.where(amax == 0, torch.ones_like(amax), amax / torch.full_like(amax, 7.0)).to(torch.bfloat16)
+    u = torch.round(wf / s.float().unsqueeze(2)).clamp(-8, 7) + 8
+    return u.to(torch.uint8).view(n, k), s
+
+
+def dequantize_w4(u: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """wd [N, K] float32 of codes ``u`` [N, K] and scales ``s`` [N, K / 128]."""
+    return (u.float() - 8.0) * s.float().repeat_interleave(W4_GROUP, dim=1)
+
+
+def linear_w4(x: torch.Tensor, u: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    return linear(x.float(), dequantize_w4(u, s)).to(x.dtype)
+
+
 # ------------------------------------------------------------------ logit processors
 # The contract of csrc/kernels/logit_processors.hip, in numpy float32.  Two per-token quantities of
 # a request drive it: in_prompt[t] (t occurs in its prompt) and n_out[t] (how often t occurs in its

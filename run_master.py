@@ -37,8 +37,9 @@ def parse(argv=None):
     ap.add_argument("--max-batch", type=int, default=None)
     ap.add_argument("--max-seq-len", type=int, default=None)
     ap.add_argument("--dtype", default=None)
-    ap.add_argument("--quant", choices=["none", "fp8"], default=None,
-                    help="fp8: workers run W8A8 e4m3 projections / experts (ops/quant.py)")
+    ap.add_argument("--quant", choices=["none", "fp8", "int4"], default=None,
+                    help="fp8: workers run W8A8 e4m3 projections / experts (ops/quant.py); int4: W4A16 dense "
+                         "projections (ops/int4.py)")
     ap.add_argument("--heartbeat-timeout", type=float, default=None)
     ap.add_argument("--auto", action="store_true", help="wait for workers, assign + distribute, no REPL prompt")
     ap.add_argument("--auto-recover", action="store_true", help="re-distribute after a worker failure")

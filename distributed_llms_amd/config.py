@@ -182,24 +182,40 @@ class ModelConfig:
             qk_norm=mt == "qwen3")
 
 
-# what models with ModelConfig.attn_bias / qk_norm (Qwen2, Qwen3) cannot run with yet
-QWEN_TP_REFUSAL = ("tensor parallelism (tp > 1) is not supported for models with a qkv bias or a q/k norm "
-                   "(Qwen2 / Qwen3): the bias shard is not built")
-QWEN_FP8_REFUSAL = ('quant="fp8" is not supported for models with a qkv bias or a q/k norm (Qwen2 / Qwen3)')
-
-
-
-def check_int4(cfg: ModelConfig, tp: int = 1) -> None:
-    """What quant="int4" (ops/int4.py) does not serve: none of it is wired or tested (ValueError)."""
-    if cfg.arch != "llama" or cfg.is_moe:
-        raise ValueError(f'quant="int4" serves dense Llama-architecture models only (arch {cfg.arch!r}, '
-                         f'{cfg.num_experts} experts)')
-    if cfg.attn_bias or cfg.qk_norm:
-        raise ValueError('quant="int4" is not supported for models with a qkv bias or a q/k norm (Qwen2 / Qwen3)')
-    if tp > 1:
-        raise ValueError('quant="int4" is not supported with tensor parallelism (tp > 1)')
-    if os.environ.get("DLLM_PP_FINE", "0") == "1":
-        raise ValueError('quant="int4" is not supported with sub-layer pipeline cuts (DLLM_PP_FINE=1)')
+def check_features(cfg: ModelConfig, *, quant: str = "none", tp: int = 1, lora: bool = False, fine_cuts: bool = False,
+                   prefix_caching: bool = False, padded_group: Optional[tuple] = None) -> None:
+    """The one table of what does not combine (ValueError): model x quant x tensor parallelism x LoRA adapters x
+    sub-layer cuts x prefix caching.  Every caller passes what it knows and leaves the rest at "absent"; the first
+    row that applies wins, so the order is part of the contract (docs/DESIGN.md, "Model stage").
+    ``fine_cuts``: the stage starts or ends inside a layer half; ``padded_group``: (real, padded) q heads per kv
+    head of a stage that pads its GQA group.  DLLM_PP_FINE (sub-layer cuts may be planned) is read here, per call."""
+    qwen = cfg.attn_bias or cfg.qk_norm
+    int4 = quant == "int4"
+    pp_fine = os.environ.get("DLLM_PP_FINE", "0") == "1"
+    pad = "(%d -> %d q heads per kv head)" % padded_group if padded_group else ""
+    table = (
+        (tp > 1 and prefix_caching, "prefix caching is not supported with tensor parallelism (tp > 1)"),
+        (tp > 1 and lora, "LoRA adapters are not supported with tensor parallelism (tp > 1)"),
+        (lora and cfg.arch == "gpt2", "LoRA adapters are not supported on GPT-2 models"),
+        (lora and quant != "none", f"LoRA adapters are not supported with quant={quant!r}"),
+        (lora and padded_group, f"LoRA adapters are not supported on a stage that pads its GQA group {pad}"),
+        (lora and pp_fine, "LoRA adapters are not supported with sub-layer pipeline cuts (DLLM_PP_FINE=1)"),
+        (int4 and (cfg.arch != "llama" or cfg.is_moe),
+         f'quant="int4" serves dense Llama-architecture models only (arch {cfg.arch!r}, {cfg.num_experts} experts)'),
+        (int4 and qwen, 'quant="int4" is not supported for models with a qkv bias or a q/k norm (Qwen2 / Qwen3)'),
+        (int4 and tp > 1, 'quant="int4" is not supported with tensor parallelism (tp > 1)'),
+        (int4 and pp_fine, 'quant="int4" is not supported with sub-layer pipeline cuts (DLLM_PP_FINE=1)'),
+        (tp > 1 and qwen, "tensor parallelism (tp > 1) is not supported for models with a qkv bias or a q/k norm "
+                          "(Qwen2 / Qwen3): the bias shard is not built"),
+        (quant == "fp8" and qwen, 'quant="fp8" is not supported for models with a qkv bias or a q/k norm (Qwen2 / Qwen3)'),
+        (fine_cuts and (cfg.arch == "gpt2" or cfg.is_moe), "sub-layer cuts need a dense SwiGLU model"),
+        (fine_cuts and tp > 1, "sub-layer cuts are not combined with tensor parallelism"),
+        (fine_cuts and padded_group, f"sub-layer cuts are not combined with a padded GQA group {pad}"),
+        (fine_cuts and lora, "LoRA adapters are not supported with sub-layer pipeline cuts"),
+    )
+    for refused, message in table:
+        if refused:
+            raise ValueError(message)
 
 
 _LLAMA3_ROPE = {"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0,
@@ -389,10 +405,7 @@ class EngineConfig:
         cfg = get_model_config(self.model if self.shard_dir is None else self.shard_dir)
         if self.num_workers > cfg.num_layers:
             raise ValueError(f"{self.num_workers} stages > {cfg.num_layers} layers")
-        if self.quant == "fp8" and (cfg.attn_bias or cfg.qk_norm):
-            raise ValueError(QWEN_FP8_REFUSAL)
-        if self.quant == "int4":
-            check_int4(cfg)
+        check_features(cfg, quant=self.quant)
         if self.lora_modules:
             if not isinstance(self.lora_modules, dict):
                 raise ValueError("lora_modules must map adapter names to sources")
@@ -402,16 +415,9 @@ class EngineConfig:
     def check_tensor_parallel(self, tp: int) -> None:
         """What a tensor-parallel layout (``tp`` ranks per stage) cannot run; every rank calls it with the
         same arguments before it builds anything, so all of them refuse together."""
-        if tp > 1 and self.enable_prefix_caching:
-            raise ValueError("prefix caching is not supported with tensor parallelism (tp > 1)")
-        if tp > 1 and self.lora_modules:
-            raise ValueError("LoRA adapters are not supported with tensor parallelism (tp > 1)")
-        if self.quant == "int4":
-            check_int4(self.model_config(), tp)
-        if tp > 1:
-            cfg = self.model_config()
-            if cfg.attn_bias or cfg.qk_norm:
-                raise ValueError(QWEN_TP_REFUSAL)
+        if tp > 1 or self.quant == "int4":     # at tp == 1 the adapters are models/lora.py check_engine's to refuse
+            check_features(self.model_config(), quant=self.quant, tp=tp, lora=tp > 1 and bool(self.lora_modules),
+                           prefix_caching=self.enable_prefix_caching)
 
     def model_config(self) -> ModelConfig:
         return get_model_config(self.shard_dir or self.model)

@@ -28,8 +28,7 @@ from .sampler import (ids_message_len, max_ids_message_len, sample_step, unpack_
 from .scheduler import Scheduler, Step
 from .logit_state import LogitState
 from ..models.lora import adapter_slots
-from .sequence import (SamplingParams, Sequence, fused_sampler_serves, request_seed, resolve_adapter,
-                       check_prompt_logprobs_head, validate_logprobs, validate_processors, validate_prompt_logprobs,
+from .sequence import (SamplingParams, Sequence, check_request, fused_sampler_serves, request_seed, resolve_adapter,
                        validate_sampling)
 
 log = logging.getLogger("dllm.engine")
@@ -115,17 +114,7 @@ class LLMEngine:
     def add_request(self, prompt: List[int], params: Optional[SamplingParams] = None,
                     request_id: Optional[str] = None) -> Sequence:
         params = params or SamplingParams()
-        if validate_logprobs(params.logprobs) is not None and self.tp is not None:
-            # the tensor-parallel lanes draw with a distributed arg-max over vocabulary shards;
-            # log-probabilities there need a distributed log-sum-exp
-            raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
-        if validate_prompt_logprobs(params.prompt_logprobs):
-            if self.tp is not None:      # the lanes hold vocabulary shards: the log-sum-exp would be distributed
-                raise ValueError("prompt_logprobs are not supported with tensor parallelism (tp > 1)")
-            check_prompt_logprobs_head(self.stage.lm_head_weight())
-        if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
-            # the processors rewrite whole logit rows; the tensor-parallel lanes hold vocabulary shards
-            raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
+        check_request(params, self.mcfg.vocab_size, tp=self.tp is not None, lm_head=self.stage.lm_head_weight())
         validate_sampling(params, self.mcfg.vocab_size, fused_sampler_serves(self.stage.device, self.stage.dtype))
         slot = resolve_adapter(params.adapter, self.adapter_slots)
         seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id,

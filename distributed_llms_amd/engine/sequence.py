@@ -175,6 +175,33 @@ def validate_processors(params, vocab_size: int) -> bool:
     return rep != 1.0 or pres != 0.0 or freq != 0.0 or bool(bias) or mt > 0
 
 
+def check_request(params, vocab_size: int, tp: bool = False, stages: int = 1, lm_head=None, stream=False) -> None:
+    """What a request cannot ask of this deployment, refused when it is admitted (ValueError) and never inside a
+    running step; the fields involved get their value checks on the way (``logit_bias`` is normalised in place).
+    ``params``: a SamplingParams, or the dict of its fields the master and the HTTP front end hold; ``tp``: the
+    sampling stage is tensor parallel; ``stages``: pipeline stages; ``lm_head``: the sampling stage's LM-head
+    weight where the caller holds it; ``stream``: the answer is streamed.  Under TP the lanes hold vocabulary shards
+    and draw with a distributed arg-max: log-probabilities would need a distributed log-sum-exp, and the processors
+    rewrite whole logit rows."""
+    get = params.get if isinstance(params, dict) else (lambda k: getattr(params, k, None))
+    if validate_logprobs(get("logprobs")) is not None:
+        if tp:
+            raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
+        if stream:
+            raise ValueError("logprobs are not available with stream")
+    if validate_prompt_logprobs(get("prompt_logprobs")):
+        if stream:
+            raise ValueError("prompt_logprobs are not available with stream")
+        if stages > 1:
+            raise ValueError("prompt_logprobs are not supported on a pipeline of more than one stage")
+        if tp:
+            raise ValueError("prompt_logprobs are not supported with tensor parallelism (tp > 1)")
+        if lm_head is not None:
+            check_prompt_logprobs_head(lm_head)
+    if validate_processors(params, vocab_size) and tp:
+        raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
+
+
 def resolve_adapter(adapter, slots: Dict[str, int]) -> int:
     """The slot of a request's ``adapter`` among the engine's adapters (``slots``: name -> slot,
     models/lora.py adapter_slots), -1 for None; an unknown name raises ValueError."""

@@ -61,7 +61,7 @@ import time
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from typing import Any, Dict, List, Tuple
 
-from ..engine.sequence import PROCESSOR_KEYS, validate_logprobs, validate_processors, validate_prompt_logprobs
+from ..engine.sequence import PROCESSOR_KEYS, check_request
 from ..utils.metrics import cluster_prometheus_text
 
 log = logging.getLogger("dllm.http")
@@ -83,12 +83,8 @@ def _sampling(body: Dict[str, Any], default_max: int = 64, max_key: str = "max_n
     p["max_new_tokens"] = int(body.get(max_key, body.get("max_new_tokens", default_max)))
     if p["max_new_tokens"] < 1:
         raise ValueError("max tokens must be >= 1")
-    validate_logprobs(p.get("logprobs"))
-    if p.get("logprobs") is not None and body.get("stream"):
-        raise ValueError("logprobs are not available with stream")
-    if validate_prompt_logprobs(p.get("prompt_logprobs")) and body.get("stream"):
-        raise ValueError("prompt_logprobs are not available with stream")
-    validate_processors(p, vocab_size)       # logit_bias arrives with string keys: {int: float} from here on
+    # logit_bias arrives with string keys: {int: float} from here on
+    check_request(p, vocab_size, stream=body.get("stream"))
     return p
 
 

@@ -32,8 +32,7 @@ import time
 from typing import Any, Dict, List, Optional, Sequence
 
 from ..config import EngineConfig, ModelConfig, get_model_config
-from ..engine.sequence import (fused_sampler_serves, resolve_adapter, validate_logprobs, validate_processors,
-                               validate_prompt_logprobs, validate_sampling)
+from ..engine.sequence import check_request, fused_sampler_serves, resolve_adapter, validate_sampling
 from ..models.lora import adapter_slots
 from ..network.protocol import MessageProtocol, pack_ids, split_prompt_logprobs, unpack_ids, unpack_result
 from ..utils.metrics import RequestMetrics
@@ -536,16 +535,10 @@ class MasterNode:
         fut: cf.Future = cf.Future()
         fut.t_submit = time.perf_counter()
         ids, params = list(prompt_ids), dict(params or {})
-        validate_logprobs(params.get("logprobs"))      # a bad value fails here, not on the stage-0 worker
-        if params.get("logprobs") is not None and params.get("stream"):
-            raise ValueError("logprobs are not available with stream")
-        if validate_prompt_logprobs(params.get("prompt_logprobs")):
-            # refused here, at admission, never inside a running step (the stage-0 worker checks again)
-            if params.get("stream"):
-                raise ValueError("prompt_logprobs are not available with stream")
-            if len(self.stage_workers) > 1:
-                raise ValueError("prompt_logprobs are not supported on a pipeline of more than one stage")
-        validate_processors(params, self.model_config.vocab_size if self.model_config else 1 << 31)     # normalises logit_bias to {int: float}
+        # a bad value or a refused combination fails here, not on the stage-0 worker (which checks again);
+        # normalises logit_bias to {int: float}
+        check_request(params, self.model_config.vocab_size if self.model_config else 1 << 31,
+                      stages=len(self.stage_workers), stream=params.get("stream"))
         resolve_adapter(params.get("adapter"), adapter_slots(self.config))     # an unknown name fails here, before dispatch
         if self.model_config:      # by the configured device; a worker on another device checks again (worker/node.py)
             from ..config import resolve_device

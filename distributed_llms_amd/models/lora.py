@@ -20,7 +20,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
-from ..config import EngineConfig, ModelConfig
+from ..config import EngineConfig, ModelConfig, check_features
 from ..ops import reference as ref
 from ..ops.lora import LoraWeight
 from . import weights as W
@@ -187,12 +187,7 @@ def check_engine(ecfg: EngineConfig, cfg: ModelConfig) -> None:
         return
     if not 1 <= ecfg.max_lora_rank <= ref.LORA_MAX_RANK:
         raise ValueError(f"max_lora_rank must be in [1, {ref.LORA_MAX_RANK}], got {ecfg.max_lora_rank}")
-    if cfg.arch == "gpt2":
-        raise ValueError("LoRA adapters are not supported on GPT-2 models")
-    if ecfg.quant != "none":
-        raise ValueError(f"LoRA adapters are not supported with quant={ecfg.quant!r}")
-    if os.environ.get("DLLM_PP_FINE", "0") == "1":
-        raise ValueError("LoRA adapters are not supported with sub-layer pipeline cuts (DLLM_PP_FINE=1)")
+    check_features(cfg, quant=ecfg.quant, lora=True)
 
 
 def adapter_slots(ecfg: EngineConfig) -> Dict[str, int]:
@@ -216,10 +211,8 @@ def build_stage_lora(stage, ecfg: EngineConfig) -> Optional[StageLora]:
     if not ecfg.lora_modules:
         return None
     check_engine(ecfg, cfg)
-    if stage.tp.enabled:
-        ecfg.check_tensor_parallel(stage.tp.size)
-    if stage.atom_start % 5 not in (0, 3) or stage.atom_end % 5 not in (0, 3):
-        raise ValueError("LoRA adapters are not supported with sub-layer pipeline cuts")
+    check_features(cfg, quant=ecfg.quant, tp=stage.tp.size, lora=True, fine_cuts=stage.fine_cuts,
+                   prefix_caching=ecfg.enable_prefix_caching)
     names = sorted(ecfg.lora_modules)
     adapters = [load_adapter(n, ecfg.lora_modules[n], cfg, ecfg.max_lora_rank) for n in names]
     rp = ref.lora_rank_pad(max(a.rank for a in adapters))

@@ -22,14 +22,9 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import knobs, ops
-from ..config import QWEN_FP8_REFUSAL, QWEN_TP_REFUSAL, ModelConfig
+from ..config import ModelConfig, check_features
 from ..ops import reference as ref
 from . import weights as W
-
-# knobs.fused_rope: decode RoPE + KV append fused into the attention kernel (one launch).  Split-K
-# partials handed to the consumer instead of reduced by a separate launch: knobs.defer_qkv (the
-# fused decode attention kernel sums them: every wave re-reads S slabs on its critical path, -3 %
-# at B=256, off), knobs.defer_o (the MLP half's add + RMSNorm, +1 %).
 
 
 @dataclass
@@ -133,8 +128,7 @@ class ModelStage:
         ``units``: [u0, u1) in units of ``unit_group`` per layer (2 halves or 5 sub-layer atoms)."""
         from ..parallel.tensor_parallel import TPGroup, check_divisible
         self.tp = tp if tp is not None else TPGroup(0, 1)
-        if self.tp.enabled and (cfg.attn_bias or cfg.qk_norm):
-            raise ValueError(QWEN_TP_REFUSAL)
+        check_features(cfg, tp=self.tp.size)
         check_divisible(cfg, self.tp.size, self.tp.moe)
         # heads this rank computes (all of them without TP)
         self.hq = cfg.num_heads // self.tp.size
@@ -149,6 +143,7 @@ class ModelStage:
         if pad_heads and cfg.arch != "gpt2":
             self.group = padded_group(self.group_real)
             self.hq = self.hkv * self.group
+        self.padded_group = (self.group_real, self.group) if self.group != self.group_real else None
         self.q_size_local = self.hq * cfg.head_dim
         g = int(unit_group)
         if units is None:
@@ -162,14 +157,9 @@ class ModelStage:
         # the same range in atoms (5 per layer)
         self.atom_start, self.atom_end = unit_to_atom(u0, g), unit_to_atom(u1, g)
         a0, a1 = self.atom_start, self.atom_end
-        if a0 % NATOM not in (0, 3) or a1 % NATOM not in (0, 3):
-            if cfg.arch == "gpt2" or cfg.is_moe:
-                raise ValueError("sub-layer cuts need a dense SwiGLU model")
-            if self.tp.enabled:
-                raise ValueError("sub-layer cuts are not combined with tensor parallelism")
-            if self.group != self.group_real:
-                raise ValueError(f"sub-layer cuts are not combined with a padded GQA group "
-                                 f"({self.group_real} -> {self.group} q heads per kv head)")
+        # a cut inside a layer half (the hand-off is then [T, H + W])
+        self.fine_cuts = a0 % NATOM not in (0, 3) or a1 % NATOM not in (0, 3)
+        check_features(cfg, tp=self.tp.size, fine_cuts=self.fine_cuts, padded_group=self.padded_group)
         self.layer_start, self.layer_end = a0 // NATOM, (a1 + NATOM - 1) // NATOM
         self.is_first = a0 == 0
         self.is_last = a1 == NATOM * cfg.num_layers
@@ -322,29 +312,16 @@ class ModelStage:
         in ``dtype``.  ``"int4"``: the dense projections become W4A16 weights (ops/int4.py), dense Llama only."""
         if mode in ("", "none", None):
             return self
-        if mode == "int4":
-            # W4A16 group-wise codes (ops/int4.py); a stage none of whose projections it takes is refused
-            from ..config import check_int4
-            from ..ops import int4
-            check_int4(self.cfg, self.tp.size)
-            if not int4.quantize_layers(self.layers):
-                raise ValueError('quant="int4" converted no weight of this stage (N and K multiples of 128)')
-            return self
-        if mode != "fp8":
-            raise ValueError(f"unknown quantization {mode!r} (none, fp8, int4)")
-        if self.cfg.attn_bias or self.cfg.qk_norm:
-            raise ValueError(QWEN_FP8_REFUSAL)
-        from ..ops import quant
-        quant.quantize_layers(self.layers)
+        check_features(self.cfg, quant=mode, tp=self.tp.size)
+        ops.quantize_layers(self.layers, mode)
         return self
 
     def load_lora(self, ecfg) -> "ModelStage":
         """The adapters of ``ecfg.lora_modules`` for this stage's layers (models/lora.py); refuses what
         cannot run with them (ValueError)."""
         from . import lora
-        if ecfg.lora_modules and self.group != self.group_real:
-            raise ValueError(f"LoRA adapters are not supported on a stage that pads its GQA group "
-                             f"({self.group_real} -> {self.group} q heads per kv head)")
+        if ecfg.lora_modules and self.padded_group:      # refused before anything of the adapters is looked at
+            check_features(self.cfg, lora=True, padded_group=self.padded_group)
         self.lora = lora.build_stage_lora(self, ecfg)
         return self
 
@@ -355,14 +332,10 @@ class ModelStage:
         w = self.lora.layers[layer - self.layer_start].get(proj)
         return y if w is None else ops.lora.apply(y, x, w, meta.lora)
 
-    @staticmethod
-    def _nbytes(t) -> int:
-        return t.nbytes() if hasattr(t, "scale") else t.numel() * t.element_size()
-
     def weight_bytes(self) -> int:
-        n = sum(self._nbytes(t) for d in self.layers for t in d.values())
-        n += sum(t.numel() * t.element_size() for t in self.embed.values())
-        n += sum(t.numel() * t.element_size() for t in self.head.values())
+        """A plain tensor's bytes, a quantized weight's own count (ops.quantize_layers), the adapters'."""
+        n = sum(t.numel() * t.element_size() if isinstance(t, torch.Tensor) else t.nbytes()
+                for d in self.layers + [self.embed, self.head] for t in d.values())
         return n + (self.lora.nbytes() if self.lora is not None else 0)
 
     def allocate_kv(self, num_blocks: int, block_size: int) -> KVCache:
@@ -437,22 +410,46 @@ class ModelStage:
                                            max_ctx=meta.max_ctx or None, workspace=meta.attn_workspace)
         return o.view(o.shape[0], self.q_size_local)
 
+    # Split-K partials handed to the consumer instead of reduced by a separate launch: knobs.defer_qkv (the fused
+    # decode attention kernel sums them: every wave re-reads S slabs on its critical path, -3 % at B=256, off),
+    # knobs.defer_o (the MLP half's add + RMSNorm, +1 %); the down projection's always go to the next add + RMSNorm.
+    # (knobs.fused_rope, decode RoPE + KV append fused into the attention kernel, is _attention's.)
+    def _proj(self, x, lw: Dict[str, torch.Tensor], layer: int, name: str, meta: Optional[BatchMeta], bias=None,
+              defer: bool = False, reduce: bool = False):
+        """The one place a dense projection of a layer runs: ``lw[name]`` through ops.linear, then the adapter
+        deltas when the step has adapter rows, then (``reduce``: the row-parallel wo / w_down) the all-reduce
+        under TP.  ``defer`` asks for the split-K partials; it survives only where nothing has to touch the dense
+        result first: no adapter rows, no bias, no TP reduce."""
+        lora = meta is not None and meta.lora is not None
+        reduce = reduce and self.tp.enabled
+        y = ops.linear(x, lw[name], bias, defer=defer and not (lora or bias is not None or reduce))
+        if lora:
+            y = self._lora(y, x, layer, name, meta)
+        return self.tp.all_reduce_(y) if reduce else y
+
+    def _pre_norm(self, h, residual: torch.Tensor, lw: Dict[str, torch.Tensor], norm: str, consumer: str):
+        """The RMSNorm in front of a half -> (x, residual): plain when nothing is pending, else fused with the add
+        of the previous half's output ``h`` (split-K partials are reduced there).  A consumer weight whose GEMM
+        takes a per-token e4m3 input (quant="fp8") gets it from the norm kernel."""
+        q8 = getattr(lw.get(consumer), "takes_fp8_act", False)
+        if h is None:
+            return ops.rms_norm(residual, lw[norm], self.cfg.norm_eps, quant_out=q8), residual
+        return ops.fused_add_rms_norm(h, residual, lw[norm], self.cfg.norm_eps, quant_out=q8)
+
     def _mlp(self, h: torch.Tensor, lw: Dict[str, torch.Tensor], layer: int = 0,
              meta: Optional[BatchMeta] = None) -> torch.Tensor:
-        if meta is not None and meta.lora is not None and not self.cfg.is_moe:
-            # adapter rows in the step: the gate|up delta must land before the activation, so the plain
-            # GEMM, the expand over both slices, then SwiGLU; the down projection materialised
-            gu = self._lora(ops.linear(h, lw["w_gate_up"]), h, layer, "w_gate_up", meta)
-            act = ops.silu_mul(gu)
-            return self._lora(ops.linear(act, lw["w_down"], defer=False), act, layer, "w_down", meta)
         if self.cfg.is_moe:
             out = ops.moe_forward(h, lw["router"], lw["experts_gate_up"], lw["experts_down"],
                                   self.cfg.experts_per_token, self.tp.expert_offset(self.cfg.num_experts))
             return self.tp.all_reduce_(out) if self.tp.enabled else out
+        if meta is not None and meta.lora is not None:
+            # adapter rows in the step: the gate|up delta must land before the activation, so the plain
+            # GEMM, the expand over both slices, then SwiGLU
+            act = ops.silu_mul(self._proj(h, lw, layer, "w_gate_up", meta))
+        else:
+            act = ops.linear_swiglu(h, lw["w_gate_up"])
         # defer: the down projection's split-K reduce is fused into the next residual-add + RMSNorm
-        # (under TP the partial [T, H] is all-reduced first, so it is materialised)
-        out = ops.linear(ops.linear_swiglu(h, lw["w_gate_up"]), lw["w_down"], defer=not self.tp.enabled)
-        return self.tp.all_reduce_(out) if self.tp.enabled else out
+        return self._proj(act, lw, layer, "w_down", meta, defer=True, reduce=True)
 
     def _units(self):
         """(is_attention_half, layer, weights) for the halves this stage runs (whole halves only)."""
@@ -486,58 +483,34 @@ class ModelStage:
         out_aux = None
         for l in range(self.layer_start, self.layer_end):
             lw = self.layers[l - self.layer_start]
-            # ---- attention half: atoms 0 (norm + qkv), 1 (attention), 2 (o-projection)
-            if self.has(l, 0) or self.has(l, 1) or self.has(l, 2):
-                a = qkv = None
-                if self.has(l, 0):
-                    # W8A8 projection next (quant="fp8"): the norm kernel emits the per-token e4m3 input
-                    q8 = isinstance(lw.get("wqkv"), ops.quant.Fp8Weight)
-                    if h is None:
-                        x = ops.rms_norm(residual, lw["attn_norm"], eps, quant_out=q8)
-                    else:
-                        x, residual = ops.fused_add_rms_norm(h, residual, lw["attn_norm"], eps, quant_out=q8)
-                    h = None
-                    prep = cfg.attn_bias or cfg.qk_norm
-                    if meta.lora is not None:
-                        # adapter rows in the step: dense projection output, then the adapter deltas
-                        qkv = self._lora(ops.linear(x, lw["wqkv"], defer=False), x, l, "wqkv", meta)
-                    else:
-                        qkv = ops.linear(x, lw["wqkv"], defer=knobs.K.defer_qkv and self.has(l, 1) and not prep)
-                    if prep:
-                        # Qwen2 qkv bias / Qwen3 per-head q, k RMSNorm, in place on the dense projection
-                        # output: attention (or the next stage, at a cut) sees prepared qkv
-                        ops.qkv_prep_(qkv, lw.get("bqkv"), lw.get("q_norm"), lw.get("k_norm"), self.hq, self.hkv,
-                                      cfg.head_dim, eps)
-                    if not self.has(l, 1):
-                        out_aux = self._dense(qkv)
-                        break
-                if self.has(l, 1):
-                    a = self._attention(qkv if qkv is not None else carry, self.kv_index[l], meta)
-                    if not self.has(l, 2):
-                        out_aux = a
-                        break
-                if self.has(l, 2):
-                    a = a if a is not None else carry
-                    # defer: a split-K o-projection's reduce is fused into the MLP half's add + RMSNorm
-                    # (TP: row-parallel partial sums, all-reduced over the group)
-                    if meta.lora is not None:
-                        h = self._lora(ops.linear(a, lw["wo"], lw.get("bo"), defer=False), a, l, "wo", meta)
-                    elif "bo" in lw:      # a Qwen3 config with attention_bias
-                        h = ops.linear(a, lw["wo"], lw["bo"])
-                    elif self.tp.enabled:
-                        h = self.tp.all_reduce_(ops.linear(a, lw["wo"]))
-                    else:
-                        h = ops.linear(a, lw["wo"], defer=knobs.K.defer_o)
+            has = [self.has(l, j) for j in range(NATOM)]
+            # ---- attention half: atoms 0 (norm + qkv), 1 (attention), 2 (o-projection); ``carry`` is the pending
+            # tensor from one atom to the next, across a cut too
+            if has[0]:
+                x, residual = self._pre_norm(h, residual, lw, "attn_norm", "wqkv")
+                h = None
+                prep = cfg.attn_bias or cfg.qk_norm
+                carry = self._proj(x, lw, l, "wqkv", meta, defer=knobs.K.defer_qkv and has[1] and not prep)
+                if prep:
+                    # Qwen2 qkv bias / Qwen3 per-head q, k RMSNorm, in place on the dense projection
+                    # output: attention (or the next stage, at a cut) sees prepared qkv
+                    ops.qkv_prep_(carry, lw.get("bqkv"), lw.get("q_norm"), lw.get("k_norm"), self.hq, self.hkv,
+                                  cfg.head_dim, eps)
+            if has[1]:
+                carry = self._attention(carry, self.kv_index[l], meta)
+            if has[2]:
+                # defer: a split-K o-projection's reduce is fused into the MLP half's add + RMSNorm
+                # (TP: row-parallel partial sums, all-reduced over the group); "bo": Qwen3 with attention_bias
+                h = self._proj(carry, lw, l, "wo", meta, bias=lw.get("bo"), defer=knobs.K.defer_o, reduce=True)
+            elif has[0] or has[1]:                    # cut after the qkv projection or after attention
+                out_aux = self._dense(carry)
+                break
             # ---- MLP half: atoms 3 / 4 (first / second half of the intermediate columns)
-            if self.has(l, 3) or self.has(l, 4):
-                q8 = isinstance(lw.get("w_gate_up"), ops.quant.Fp8Weight)
-                if h is None:
-                    x = ops.rms_norm(residual, lw["mlp_norm"], eps, quant_out=q8)
-                else:
-                    x, residual = ops.fused_add_rms_norm(h, residual, lw["mlp_norm"], eps, quant_out=q8)
-                if self.has(l, 3) and self.has(l, 4):
+            if has[3] or has[4]:
+                x, residual = self._pre_norm(h, residual, lw, "mlp_norm", "w_gate_up")
+                if has[3] and has[4]:
                     h = self._mlp(x, lw, l, meta)
-                elif self.has(l, 3):                  # cut between the MLP halves: hand over the partial sum
+                elif has[3]:                          # cut between the MLP halves: hand over the partial sum
                     out_aux = self._dense(self._mlp(x, lw))
                     h = None
                     break
@@ -549,37 +522,33 @@ class ModelStage:
             return ops.add_(residual, self._dense(h))
         return self._logits(h, residual, meta)
 
-    def _logits(self, h, residual: torch.Tensor, meta: BatchMeta) -> torch.Tensor:
+    def _final_norm(self, h: torch.Tensor, residual: Optional[torch.Tensor], idx: Optional[torch.Tensor]):
+        """The final norm over rows ``idx`` (None: all) of the last layer's output ``h`` and the residual stream
+        (GPT-2: ``h`` is the stream, LayerNorm)."""
+        cfg = self.cfg
+        if idx is not None:
+            h = h.index_select(0, idx)
+            residual = None if residual is None else residual.index_select(0, idx)
+        if cfg.arch == "gpt2":
+            return ops.layer_norm(h, self.head["final_norm"], self.head["final_norm_b"], cfg.norm_eps)
+        return ops.fused_add_rms_norm(h, residual, self.head["final_norm"], cfg.norm_eps)[0]
+
+    def _logits(self, h, residual: Optional[torch.Tensor], meta: BatchMeta) -> torch.Tensor:
         # ``h`` may still be the last down projection's split-K partials: at decode (every row's
         # logits) they are reduced inside the final add + RMSNorm, as between layers
-        cfg = self.cfg
-        if meta.logits_idx is not None or cfg.arch == "gpt2":
+        if meta.logits_idx is not None or self.cfg.arch == "gpt2":
             h = self._dense(h)
         if meta.score_idx is not None:
             self._score(h, residual, meta)
-        if meta.logits_idx is not None:
-            h = h.index_select(0, meta.logits_idx)
-            residual = residual.index_select(0, meta.logits_idx)
-        if cfg.arch == "gpt2":
-            x = ops.layer_norm(h, self.head["final_norm"], self.head["final_norm_b"], cfg.norm_eps)
-        else:
-            x, _ = ops.fused_add_rms_norm(h, residual, self.head["final_norm"], cfg.norm_eps)
-        return ops.linear(x, self.lm_head_weight())
+        return ops.linear(self._final_norm(h, residual, meta.logits_idx), self.lm_head_weight())
 
     def _score(self, h: torch.Tensor, residual: Optional[torch.Tensor], meta: BatchMeta) -> None:
         """Prompt scoring: the final norm over the asking rows of the last layer's output, then the fused
         LM-head log-likelihood op with each row's next prompt token -- no logits of those rows exist."""
-        cfg = self.cfg
         w = self.lm_head_weight()
         if self.tp.enabled or not isinstance(w, torch.Tensor):
             raise RuntimeError("prompt scoring needs the whole, plain LM head on the sampling stage")
-        h = h.index_select(0, meta.score_idx)
-        if cfg.arch == "gpt2":
-            x = ops.layer_norm(h, self.head["final_norm"], self.head["final_norm_b"], cfg.norm_eps)
-        else:
-            x, _ = ops.fused_add_rms_norm(h, residual.index_select(0, meta.score_idx), self.head["final_norm"],
-                                          cfg.norm_eps)
-        meta.prompt_lp = ops.lm_head_logprobs(x, w, meta.score_targets)
+        meta.prompt_lp = ops.lm_head_logprobs(self._final_norm(h, residual, meta.score_idx), w, meta.score_targets)
 
     def _forward_gpt2(self, inp: torch.Tensor, meta: BatchMeta) -> torch.Tensor:
         cfg = self.cfg
@@ -599,11 +568,4 @@ class ModelStage:
                 h = ops.layer_norm(x, lw["ln2_w"], lw["ln2_b"], eps)
                 f = ops.gelu_tanh(ops.linear(h, lw["w_fc"], lw["b_fc"]))
                 x = ops.add_(x, ops.linear(f, lw["w_proj"], lw["b_proj"]))
-        if not self.is_last:
-            return x
-        if meta.score_idx is not None:
-            self._score(x, None, meta)
-        if meta.logits_idx is not None:
-            x = x.index_select(0, meta.logits_idx)
-        x = ops.layer_norm(x, self.head["final_norm"], self.head["final_norm_b"], eps)
-        return ops.linear(x, self.lm_head_weight())
+        return self._logits(x, None, meta) if self.is_last else x

@@ -27,6 +27,7 @@ __all__ = [
     "paged_attention_prefill_rope", "sample_rows", "token_logprobs", "lm_head_logprobs", "lm_head_ranges",
     "logit_state_update",
     "apply_logit_processors", "logit_state_count", "prefill_split_plan", "prefill_split_eligible", "qkv_prep_",
+    "quantize_layers",
 ]
 
 
@@ -169,16 +170,11 @@ def gelu_tanh(x):
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, defer: bool = False):
     """y = x @ w^T (+bias). w is [N, K].  ``defer`` (GPU): the result may come back as a
     :class:`gemm.SplitKPartial` for ``fused_add_rms_norm`` to reduce (or ``materialize()``).
-    ``w`` may be a :class:`quant.Fp8Weight` (W8A8 e4m3 GEMM, no bias) or an :class:`int4.Int4Weight` (W4A16, no
-    bias, always a dense result)."""
-    if isinstance(w, quant.Fp8Weight):
-        if bias is not None:
-            raise ValueError("linear: fp8 weights take no bias")
-        return quant.linear_fp8(x, w, defer=defer)
-    if isinstance(w, int4.Int4Weight):
-        if bias is not None:
-            raise ValueError("linear: int4 weights take no bias")
-        return int4.linear_int4(x, w, defer=defer)
+    ``w`` may be a quantized weight (:func:`quantize_layers`), which then runs its own ``linear()``: a
+    :class:`quant.Fp8Weight` (W8A8 e4m3 GEMM, no bias) or an :class:`int4.Int4Weight` (W4A16, no bias, always a
+    dense result)."""
+    if not isinstance(w, torch.Tensor):          # a quantized weight runs its own GEMM
+        return w.linear(x, bias, defer)
     if not _gpu(x):
         return ref.linear(x, w, bias)
     return gemm.linear(x, w, bias, defer=defer)
@@ -186,15 +182,30 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
 
 def linear_swiglu(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
     """silu(x @ Wg^T) * (x @ Wu^T), W = [Wg; Wu]; fused into the GEMM epilogue on the GPU (decode)."""
-    if isinstance(w_gate_up, quant.Fp8Weight):
-        return quant.linear_fp8(x, w_gate_up, swiglu=True)
-    if isinstance(w_gate_up, int4.Int4Weight):
-        return silu_mul(int4.linear_int4(x, w_gate_up))
+    if not isinstance(w_gate_up, torch.Tensor):
+        return w_gate_up.linear(x, swiglu=True)
     if _gpu(x):
         y = gemm.linear_swiglu(x, w_gate_up)
         if y is not None:                    # None: gemm.route found no fused kernel (GemmRoute.unfused)
             return y
     return silu_mul(linear(x, w_gate_up))
+
+
+QUANT_MODULES = {"fp8": quant, "int4": int4}      # EngineConfig.quant -> the module of its weight format
+
+
+def quantize_layers(layers, mode: str) -> int:
+    """Replace the dense projections (quant.QUANT_KEYS; fp8: the MoE expert stacks too) of every layer dict by
+    ``mode``'s weight objects, in place; returns how many were converted.  A quantized weight offers ``shape /
+    device / dtype / numel() / nbytes() / dequantize()``, ``takes_fp8_act`` and the ``linear()`` that
+    :func:`linear` / :func:`linear_swiglu` hand over to."""
+    if mode not in QUANT_MODULES:
+        raise ValueError(f"unknown quantization {mode!r} (none, fp8, int4)")
+    mod = QUANT_MODULES[mode]
+    n = mod.quantize_layers(layers, quant.QUANT_KEYS)
+    if not n and getattr(mod, "NOTHING_CONVERTED", None):
+        raise ValueError(mod.NOTHING_CONVERTED)
+    return n
 
 
 def add_(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -25,8 +25,10 @@ import torch
 from .. import _ext
 from . import gemm
 from . import reference as ref
+from .quant import QUANT_KEYS
 
-QUANT_KEYS = ("wqkv", "wo", "w_gate_up", "w_down")
+# ops.quantize_layers refuses a stage none of whose projections this format takes
+NOTHING_CONVERTED = 'quant="int4" converted no weight of this stage (N and K multiples of 128)'
 GROUP = ref.W4_GROUP
 
 # From this M the op dequantizes and runs the bf16 GEMMs.  bench/int4_bench.py (profiles/int4.md): the smallest
@@ -63,6 +65,7 @@ class Int4Weight:
     scales ``scale`` ([N / 16, K / 128, 16]): w ~= (code - 8) * scale."""
 
     __slots__ = ("packed", "scale")
+    takes_fp8_act = False        # W4A16: activations stay bf16
 
     def __init__(self, packed: torch.Tensor, scale: torch.Tensor):
         if packed.dtype != torch.uint8 or packed.dim() != 3 or packed.shape[2] != 1024 or packed.shape[0] % 8 \
@@ -99,6 +102,16 @@ class Int4Weight:
 
     def dequantize(self, dtype=torch.float32) -> torch.Tensor:
         return ref.dequantize_w4(self.codes(), self.scales()).to(dtype)
+
+    def linear(self, x, bias=None, defer: bool = False, swiglu: bool = False):
+        """What ops.linear / ops.linear_swiglu do with this weight: always dense, SwiGLU as silu_mul on the result."""
+        if bias is not None:
+            raise ValueError("linear: int4 weights take no bias")
+        y = linear_int4(x, self, defer=defer)
+        if swiglu:
+            from . import silu_mul
+            return silu_mul(y)
+        return y
 
     def __repr__(self):
         return f"Int4Weight(shape={tuple(self.shape)}, device={self.device})"

@@ -37,7 +37,7 @@ from . import gemm
 
 FP8 = torch.float8_e4m3fn
 FP8_MAX = 448.0
-QUANT_KEYS = ("wqkv", "wo", "w_gate_up", "w_down")
+QUANT_KEYS = ("wqkv", "wo", "w_gate_up", "w_down")      # the dense projections every quantized format converts
 EXPERT_KEYS = ("experts_gate_up", "experts_down")
 
 
@@ -46,6 +46,7 @@ class Fp8Weight:
     w ~= q * scale[:, None]."""
 
     __slots__ = ("q", "scale")
+    takes_fp8_act = True         # its GEMM reads a per-token e4m3 input: the norm before it may emit an Fp8Act
 
     def __init__(self, q: torch.Tensor, scale: torch.Tensor):
         if q.dtype != FP8 or q.dim() != 2 or scale.shape != (q.shape[0],) or scale.dtype != torch.float32:
@@ -72,6 +73,12 @@ class Fp8Weight:
 
     def dequantize(self, dtype=torch.float32) -> torch.Tensor:
         return (self.q.float() * self.scale[:, None]).to(dtype)
+
+    def linear(self, x, bias=None, defer: bool = False, swiglu: bool = False):
+        """What ops.linear / ops.linear_swiglu do with this weight."""
+        if bias is not None:
+            raise ValueError("linear: fp8 weights take no bias")
+        return linear_fp8(x, self, swiglu=swiglu, defer=defer)
 
     def __repr__(self):
         return f"Fp8Weight(shape={tuple(self.q.shape)}, device={self.q.device})"

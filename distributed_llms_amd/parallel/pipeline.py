@@ -38,8 +38,8 @@ from ..engine.runner import StageRunner
 from ..engine.sampler import ids_message_len, sample_step, unpack_ids_message
 from ..engine.scheduler import Scheduler, Step
 from ..engine.logit_state import LogitState
-from ..engine.sequence import (SamplingParams, Sequence, fused_sampler_serves, request_seed, resolve_adapter,
-                               validate_logprobs, validate_processors, validate_prompt_logprobs, validate_sampling)
+from ..engine.sequence import (SamplingParams, Sequence, check_request, fused_sampler_serves, request_seed,
+                               resolve_adapter, validate_sampling)
 from ..models.lora import adapter_slots
 from ..utils.tracing import get_tracer
 from .comm import STOP, PendingIds, Transport
@@ -139,12 +139,7 @@ class PipelineDriver:
     def add_request(self, prompt: List[int], params: Optional[SamplingParams] = None,
                     request_id: Optional[str] = None) -> Sequence:
         params = params or SamplingParams()
-        if validate_logprobs(params.logprobs) is not None and self.tp is not None:
-            raise ValueError("logprobs are not supported with tensor parallelism (tp > 1)")
-        if validate_prompt_logprobs(params.prompt_logprobs):      # a driver exists only with two stages or more
-            raise ValueError("prompt_logprobs are not supported on a pipeline of more than one stage")
-        if validate_processors(params, self.mcfg.vocab_size) and self.tp is not None:
-            raise ValueError("logit processors are not supported with tensor parallelism (tp > 1)")
+        check_request(params, self.mcfg.vocab_size, tp=self.tp is not None, stages=self.t.num_stages)
         # the last stage samples: stages of one pipeline share a device type and dtype
         validate_sampling(params, self.mcfg.vocab_size, fused_sampler_serves(self.device, self.runner.stage.dtype))
         seq = Sequence(list(prompt), params, eos_token_id=self.mcfg.eos_token_id, request_id=request_id,

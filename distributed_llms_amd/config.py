@@ -41,6 +41,9 @@ class ModelConfig:
     eos_token_id: int = 2
     attn_bias: bool = False        # Qwen2 / Qwen2.5: bias on the q, k and v projections
     qk_norm: bool = False          # Qwen3: RMSNorm over head_dim on every q and k head, before RoPE
+    # the checkpoint's ``quantization_config`` (an AWQ or GPTQ 4-bit checkpoint, check_quantization); served with
+    # EngineConfig.quant = "int4" only
+    quantization: Optional[Dict[str, Any]] = None
 
     # ------------------------------------------------------------------ sizes
     @property
@@ -133,6 +136,8 @@ class ModelConfig:
         if self.is_moe:
             d["num_local_experts"] = self.num_experts
             d["num_experts_per_tok"] = self.experts_per_token
+        if self.quantization:
+            d["quantization_config"] = dict(self.quantization)
         return d
 
     @staticmethod
@@ -179,7 +184,42 @@ class ModelConfig:
             experts_per_token=cfg.get("num_experts_per_tok", 0) if mt == "mixtral" else 0,
             bos_token_id=cfg.get("bos_token_id", 1), eos_token_id=eos,
             attn_bias=mt == "qwen2" or (mt == "qwen3" and bool(cfg.get("attention_bias", False))),
-            qk_norm=mt == "qwen3")
+            qk_norm=mt == "qwen3",
+            quantization=dict(cfg["quantization_config"]) if check_quantization(cfg.get("quantization_config")) else None)
+
+
+def check_quantization(q: Optional[Dict[str, Any]]) -> Optional[str]:
+    """The weight format of a checkpoint's ``quantization_config`` (ops/int4.py from_checkpoint: "awq", "gptq" or
+    "gptq_v2"; None for none), or a ValueError naming the field that is not served: 4 bits, groups of 128 along K,
+    AWQ with zero points in the "gemm" packing, GPTQ without act-order."""
+    if not q:
+        return None
+    method = q.get("quant_method")
+    if method not in ("awq", "gptq"):
+        raise ValueError(f"quantization_config: quant_method {method!r} is not supported (awq, gptq)")
+    if q.get("bits") != 4:
+        raise ValueError(f"quantization_config ({method}): bits {q.get('bits')!r} is not supported (4)")
+    if q.get("group_size") != 128:
+        raise ValueError(f"quantization_config ({method}): group_size {q.get('group_size')!r} is not supported (128)")
+    if method == "awq":
+        if q.get("zero_point", True) is not True:
+            raise ValueError(f"quantization_config (awq): zero_point {q.get('zero_point')!r} is not supported (true)")
+        if str(q.get("version", "gemm")).lower() != "gemm":
+            raise ValueError(f"quantization_config (awq): version {q.get('version')!r} is not supported (gemm)")
+        return "awq"
+    if q.get("desc_act", False):
+        raise ValueError("quantization_config (gptq): desc_act true (act-order) is not supported")
+    fmt = q.get("checkpoint_format", "gptq")
+    if fmt not in ("gptq", "gptq_v2"):
+        raise ValueError(f"quantization_config (gptq): checkpoint_format {fmt!r} is not supported (gptq, gptq_v2)")
+    return fmt
+
+
+def check_quantized_checkpoint(cfg: ModelConfig, quant: str) -> None:
+    """A 4-bit checkpoint holds no weights another ``quant`` could start from."""
+    if cfg.quantization and quant != "int4":
+        raise ValueError(f"model {cfg.name!r} is a {cfg.quantization.get('quant_method')} 4-bit checkpoint: "
+                         f'pass quant="int4" (--quant int4), not quant={quant!r}')
 
 
 def check_features(cfg: ModelConfig, *, quant: str = "none", tp: int = 1, lora: bool = False, fine_cuts: bool = False,
@@ -406,6 +446,7 @@ class EngineConfig:
         if self.num_workers > cfg.num_layers:
             raise ValueError(f"{self.num_workers} stages > {cfg.num_layers} layers")
         check_features(cfg, quant=self.quant)
+        check_quantized_checkpoint(cfg, self.quant)
         if self.lora_modules:
             if not isinstance(self.lora_modules, dict):
                 raise ValueError("lora_modules must map adapter names to sources")

@@ -42,6 +42,7 @@ PYBIND11_MODULE(_C_kernels, m) {
   m.def("gemm_sq", &dllm::gemm_sq);
   m.def("gemm_w4a16", &dllm::gemm_w4a16);
   m.def("dequant_w4", &dllm::dequant_w4);
+  m.def("w4_repack", &dllm::w4_repack);
   m.def("gemm_pp_moe", &dllm::gemm_pp_moe);
   m.def("gemm_pp", &dllm::gemm_pp);
   m.def("gemm_pf", &dllm::gemm_pf);

@@ -29,6 +29,16 @@
 //  * split-K: slices write f32 partials [S, M, N] to the workspace, w4_reduce sums them in slice order and
 //    rounds once -- no atomics, the same bits on every launch, graph-capturable.  One slice stores bf16.
 //
+// Zero-point variant (template parameter ZP; AWQ / GPTQ checkpoints, ops/int4.py from_checkpoint):
+// wd[n, k] = (u[n, k] - z[n, k / 128]) * f32(s[n, k / 128]) with an integer z in 0..15 and an f16 or bf16 s.  Both
+// live in ONE dword per (row, group), u32 [N / 16, K / 128, 16] in place of the bf16 scales: the f32 value of s
+// (exact for f16 and bf16, whose low 13 mantissa bits are then zero) with z in bits 0..3 -- so the kernels never
+// see the scale's dtype, s is `dword & ~15` and z is `dword & 15`.  A lane needs the scales of its four
+// accumulator rows 4 (l / 16) .. + 3 (one 16-byte load, as the symmetric kernel's 8-byte one) and the zero of its
+// fragment row l % 16 (one more dword of the same 64-byte line).  code | 0x4300 stays; the offset that comes off in
+// f32 is 128 + z, the difference -15..15 is exact in bf16, and the scale is still applied once per group and
+// accumulator register.  The symmetric instantiations (ZP = false) are the code they were.
+//
 // dequant_w4: the whole weight to bf16_rne(wd) in plain [N, K] order for the large-M route (the existing bf16
 // GEMMs then serve it): one wave per 1 KiB block, every store instruction writes 4 rows x 256 bytes.
 #include "common.h"
@@ -46,12 +56,13 @@ constexpr int QBM = 64, QBN = 128, QG = 128;       // x rows / weight rows per t
 constexpr int QXTILE = QBM * QG;                    // bf16 elements of one x tile (16 KiB)
 
 // one K-step's A fragment (8 bf16 of one weight row) from its packed word
-__device__ __forceinline__ bf16x8 w4_frag(uint32_t w) {
+// (`off`: 128 + the zero point)
+__device__ __forceinline__ bf16x8 w4_frag(uint32_t w, float off) {
   bf16x8 f;
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     const uint32_t pair = ((w >> (4 * p)) & 0x000F000Fu) | 0x43004300u;      // bf16 (128 + u) x 2
-    const float lo = __uint_as_float(pair << 16) - 136.f, hi = __uint_as_float(pair & 0xFFFF0000u) - 136.f;
+    const float lo = __uint_as_float(pair << 16) - off, hi = __uint_as_float(pair & 0xFFFF0000u) - off;
     f[2 * p] = f2bf(lo);
     f[2 * p + 1] = f2bf(hi);
   }
@@ -59,10 +70,13 @@ __device__ __forceinline__ bf16x8 w4_frag(uint32_t w) {
 }
 }  // namespace
 
-template <int CT, bool SPLIT>
+// ZP: `Scv` is the u32 scale | zero array, else the bf16 scales
+template <int CT, bool SPLIT, bool ZP>
 __global__ void __launch_bounds__(256) gemm_w4a16_kernel(bf16* __restrict__ C, float* __restrict__ P,
                                                          const bf16* __restrict__ X, const uint8_t* __restrict__ Wp,
-                                                         const bf16* __restrict__ Sc, int M, int N, int K, int gps) {
+                                                         const void* __restrict__ Scv, int M, int N, int K, int gps) {
+  const bf16* __restrict__ Sc = static_cast<const bf16*>(Scv);
+  const uint32_t* __restrict__ Sz = static_cast<const uint32_t*>(Scv);
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * QXTILE];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int fr = lane & 15, fq = lane >> 4;
@@ -86,12 +100,19 @@ __global__ void __launch_bounds__(256) gemm_w4a16_kernel(bf16* __restrict__ C, f
   };
   u32x4q wq[2];
   bf16x4 sq[2];
+  u32x4q zq[2];           // ZP: the four scale | zero dwords of the accumulator rows, and the fragment row's
+  uint32_t zr[2];
   auto load_w = [&](int g) {
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
       const size_t blk = (t0 + a) * G + g;
       wq[a] = __builtin_nontemporal_load(reinterpret_cast<const u32x4q*>(Wp + blk * 1024) + lane);
-      sq[a] = *reinterpret_cast<const bf16x4*>(Sc + blk * 16 + 4 * fq);
+      if constexpr (ZP) {
+        zq[a] = *reinterpret_cast<const u32x4q*>(Sz + blk * 16 + 4 * fq);
+        zr[a] = Sz[blk * 16 + fr];
+      } else {
+        sq[a] = *reinterpret_cast<const bf16x4*>(Sc + blk * 16 + 4 * fq);
+      }
     }
   };
 
@@ -111,6 +132,12 @@ __global__ void __launch_bounds__(256) gemm_w4a16_kernel(bf16* __restrict__ C, f
     __syncthreads();
     const u32x4q wc[2] = {wq[0], wq[1]};
     const bf16x4 sc[2] = {sq[0], sq[1]};
+    const u32x4q zc[2] = {zq[0], zq[1]};
+    float off[2] = {136.f, 136.f};
+    if constexpr (ZP) {
+      off[0] = (float)(128u + (zr[0] & 15u));
+      off[1] = (float)(128u + (zr[1] & 15u));
+    }
     if (g + 1 < g1) {
       stage(cur ^ 1, g + 1);
       load_w(g + 1);
@@ -129,7 +156,7 @@ __global__ void __launch_bounds__(256) gemm_w4a16_kernel(bf16* __restrict__ C, f
         fb[ct] = *reinterpret_cast<const bf16x8*>(xs + (ct * 16 + fr) * QG + (((4 * j + fq) ^ fr) * 8));
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
-        const bf16x8 fa = w4_frag(wc[a][j]);
+        const bf16x8 fa = w4_frag(wc[a][j], off[a]);
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
           ga[a][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[ct], ga[a][ct], 0, 0, 0);
@@ -139,7 +166,7 @@ __global__ void __launch_bounds__(256) gemm_w4a16_kernel(bf16* __restrict__ C, f
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float s = bf2f(sc[a][i]);
+        const float s = ZP ? __uint_as_float(zc[a][i] & ~15u) : bf2f(sc[a][i]);
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) acc[a][ct][i] += s * ga[a][ct][i];
       }
@@ -174,8 +201,9 @@ __global__ void __launch_bounds__(256) w4_reduce_kernel(bf16* __restrict__ C, co
 }
 
 // one wave per (16-row tile, group) block; store `it` writes rows 4 it .. 4 it + 3, 16 chunks of 8 k each
+template <bool ZP>
 __global__ void __launch_bounds__(256) dequant_w4_kernel(bf16* __restrict__ W, const uint32_t* __restrict__ Wp,
-                                                         const bf16* __restrict__ Sc, int K, size_t nblk) {
+                                                         const void* __restrict__ Scv, int K, size_t nblk) {
   const int lane = threadIdx.x & 63;
   const size_t blk = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (blk >= nblk) return;
@@ -186,16 +214,24 @@ __global__ void __launch_bounds__(256) dequant_w4_kernel(bf16* __restrict__ W, c
   for (int it = 0; it < 4; ++it) {
     const int r = 4 * it + (lane >> 4);
     const uint32_t w = Wp[blk * 256 + (r + 16 * q) * 4 + j];
-    const float s = bf2f(Sc[blk * 16 + r]);
+    float s;
+    int z = 8;
+    if constexpr (ZP) {
+      const uint32_t d = static_cast<const uint32_t*>(Scv)[blk * 16 + r];
+      s = __uint_as_float(d & ~15u);
+      z = (int)(d & 15u);
+    } else {
+      s = bf2f(static_cast<const bf16*>(Scv)[blk * 16 + r]);
+    }
     bf16x8 o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = f2bf((float)((int)((w >> (4 * (e >> 1) + 16 * (e & 1))) & 15u) - 8) * s);
+    for (int e = 0; e < 8; ++e) o[e] = f2bf((float)((int)((w >> (4 * (e >> 1) + 16 * (e & 1))) & 15u) - z) * s);
     *reinterpret_cast<bf16x8*>(W + (t * 16 + r) * K + g * QG + c * 8) = o;
   }
 }
 
 int gemm_w4a16(uintptr_t c, uintptr_t x, uintptr_t wp, uintptr_t scale, uintptr_t ws, long ws_floats, int M, int N,
-               int K, int splits, uintptr_t stream) {
+               int K, int splits, int zp, uintptr_t stream) {
   DLLM_HOST_CHECK(M >= 1 && M <= (1 << 20), "1 <= M <= 2^20");
   DLLM_HOST_CHECK(N >= QBN && N % QBN == 0 && K >= QG && K % QG == 0, "N % 128 and K % 128");
   DLLM_HOST_CHECK(c != 0 && x != 0 && wp != 0 && scale != 0, "null operand");
@@ -206,9 +242,12 @@ int gemm_w4a16(uintptr_t c, uintptr_t x, uintptr_t wp, uintptr_t scale, uintptr_
   const dim3 grid(N / QBN, (M + QBM - 1) / QBM, p.S);
   dispatch_value<1, 2, 4>(M <= 16 ? 1 : M <= 32 ? 2 : 4, "gemm_w4a16: column fragments", [&](auto ct) {
     dispatch_value<0, 1>(p.S > 1, "gemm_w4a16: split", [&](auto sp) {
-      hipLaunchKernelGGL((gemm_w4a16_kernel<decltype(ct)::value, decltype(sp)::value != 0>), grid, dim3(256), 0, s,
-                         (bf16*)c, (float*)ws, (const bf16*)x, (const uint8_t*)wp, (const bf16*)scale, M, N, K,
-                         p.kts);
+      dispatch_value<0, 1>(zp != 0, "gemm_w4a16: zero points", [&](auto z) {
+        hipLaunchKernelGGL(
+            (gemm_w4a16_kernel<decltype(ct)::value, decltype(sp)::value != 0, decltype(z)::value != 0>), grid,
+            dim3(256), 0, s, (bf16*)c, (float*)ws, (const bf16*)x, (const uint8_t*)wp, (const void*)scale, M, N, K,
+            p.kts);
+      });
     });
   });
   DLLM_HIP_CHECK(hipGetLastError());
@@ -221,13 +260,15 @@ int gemm_w4a16(uintptr_t c, uintptr_t x, uintptr_t wp, uintptr_t scale, uintptr_
   return p.S;
 }
 
-void dequant_w4(uintptr_t out, uintptr_t wp, uintptr_t scale, int N, int K, uintptr_t stream) {
+void dequant_w4(uintptr_t out, uintptr_t wp, uintptr_t scale, int N, int K, int zp, uintptr_t stream) {
   DLLM_HOST_CHECK(N >= QBN && N % QBN == 0 && K >= QG && K % QG == 0, "N % 128 and K % 128");
   DLLM_HOST_CHECK(out != 0 && wp != 0 && scale != 0, "null operand");
   const size_t nblk = (size_t)(N / 16) * (K / QG);
-  hipLaunchKernelGGL(dequant_w4_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), (bf16*)out, (const uint32_t*)wp, (const bf16*)scale, K,
-                     nblk);
+  dispatch_value<0, 1>(zp != 0, "dequant_w4: zero points", [&](auto z) {
+    hipLaunchKernelGGL(dequant_w4_kernel<decltype(z)::value != 0>, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), (bf16*)out, (const uint32_t*)wp, (const void*)scale, K,
+                       nblk);
+  });
   DLLM_HIP_CHECK(hipGetLastError());
 }
 

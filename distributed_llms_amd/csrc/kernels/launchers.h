@@ -84,10 +84,16 @@ int gemm_sq(uintptr_t c, uintptr_t a, uintptr_t b, uintptr_t ws, long ws_floats,
             int mode, int variant, uintptr_t stream);
 // gemm_w4.hip: c [M, N] bf16 = x [M, K] bf16 . wd^T with int4 weights wp (fragment-packed, N K / 2 bytes) and bf16
 // group scales [N / 16, K / 128, 16]; N % 128 == 0, K % 128 == 0.  ws: f32 [S, M, N] partials of the S K slices
-// (returned; 1: none).  dequant_w4: the same weight to bf16 [N, K]
+// (returned; 1: none).  dequant_w4: the same weight to bf16 [N, K].  zp != 0: `scale` is the zero-point variant's
+// u32 [N / 16, K / 128, 16] array, f32 scale bits | zero point 0..15 in bits 0..3
 int gemm_w4a16(uintptr_t c, uintptr_t x, uintptr_t wp, uintptr_t scale, uintptr_t ws, long ws_floats, int M, int N,
-               int K, int splits, uintptr_t stream);
-void dequant_w4(uintptr_t out, uintptr_t wp, uintptr_t scale, int N, int K, uintptr_t stream);
+               int K, int splits, int zp, uintptr_t stream);
+void dequant_w4(uintptr_t out, uintptr_t wp, uintptr_t scale, int N, int K, int zp, uintptr_t stream);
+// w4_repack.hip: an AWQ (fmt 0), GPTQ v1 (1) or GPTQ v2 (2) projection (qweight / qzeros i32, scales f16 or bf16
+// [K / 128, N]; N % 128 == 0, K % 128 == 0) into rows row0 .. row0 + N of a [dstN, K] weight: fragment-packed codes
+// `wp` and the scale | zero dwords `sz`
+void w4_repack(uintptr_t wp, uintptr_t sz, uintptr_t qweight, uintptr_t qzeros, uintptr_t scales, int fmt,
+               int scale_bf16, int N, int K, int dstN, int row0, uintptr_t stream);
 
 void moe_route(uintptr_t logits, int T, int E, int k, uintptr_t topk_w, uintptr_t topk_ids, uintptr_t counts,
                uintptr_t offsets, uintptr_t sorted_tok, uintptr_t inv, uintptr_t stream);

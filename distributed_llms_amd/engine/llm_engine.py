@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import _ext, knobs
-from ..config import EngineConfig, resolve_device, torch_dtype
+from ..config import EngineConfig, check_quantized_checkpoint, resolve_device, torch_dtype
 from ..models.stage import ModelStage
 from .batch import build_host_batch
 from .graphs import SCRATCH_SEQ_ID
@@ -47,13 +47,18 @@ def make_block_manager(num_blocks: int, block_size: int, prefix_caching: bool = 
 def build_stage(ecfg: EngineConfig, layer_start: int = 0, layer_end: Optional[int] = None,
                 device: Optional[str] = None, shard_state=None, units=None, tp=None,
                 unit_group: int = 2) -> ModelStage:
-    """``units`` / ``unit_group``: the stage's unit range (parallel/planner.py StagePlan)."""
+    """``units`` / ``unit_group``: the stage's unit range (parallel/planner.py StagePlan).  Without a
+    ``shard_state``, a 4-bit checkpoint directory (``ecfg.model``) is read here; any other model is synthetic."""
     mcfg = ecfg.model_config()
+    check_quantized_checkpoint(mcfg, ecfg.quant)        # before anything of it is read
     layer_end = mcfg.num_layers if layer_end is None else layer_end
     dev = resolve_device(device or ecfg.device)
     dtype = torch_dtype(ecfg.dtype)
     stage = ModelStage(mcfg, layer_start, layer_end, device=dev, dtype=dtype, units=units, tp=tp,
                        unit_group=unit_group)
+    if shard_state is None and mcfg.quantization and ecfg.shard_dir is None and os.path.isdir(ecfg.model):
+        from ..checkpoint.shard_manager import iter_checkpoint
+        shard_state = dict(iter_checkpoint(ecfg.model))
     if shard_state is not None:
         stage.load_hf_state(shard_state)
     else:

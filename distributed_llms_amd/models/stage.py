@@ -22,7 +22,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import knobs, ops
-from ..config import ModelConfig, check_features
+from ..config import ModelConfig, check_features, check_quantized_checkpoint
 from ..ops import reference as ref
 from . import weights as W
 
@@ -289,10 +289,16 @@ class ModelStage:
         return self
 
     def load_hf_state(self, sd: Dict[str, torch.Tensor]) -> "ModelStage":
-        """Load from HF-named tensors (a shard file's dict); fuses q|k|v and gate|up."""
+        """Load from HF-named tensors (a shard file's dict); fuses q|k|v and gate|up.  The projections of an AWQ /
+        GPTQ 4-bit checkpoint (``cfg.quantization``) arrive as int4 weights, repacked on the stage's device."""
         cfg = self.cfg
-        conv = lambda t: t.to(device=self.device, dtype=self.dtype).contiguous()
-        self.layers = [{k: conv(v) for k, v in W.hf_to_block(cfg, l, sd).items() if self._keep(l, k)}
+        if cfg.quantization:
+            check_features(cfg, quant="int4", tp=self.tp.size)
+            if self.padded_group or self.fine_cuts:
+                raise ValueError("a 4-bit checkpoint is not loaded into a stage that pads its GQA group or starts or "
+                                 "ends inside a layer")
+        conv = lambda t: t.to(device=self.device, dtype=self.dtype).contiguous() if isinstance(t, torch.Tensor) else t
+        self.layers = [{k: conv(v) for k, v in W.hf_to_block(cfg, l, sd, self.device).items() if self._keep(l, k)}
                        for l in range(self.layer_start, self.layer_end)]
         self._pad_heads()
         self._slice_mlp_halves()
@@ -309,7 +315,9 @@ class ModelStage:
     def quantize(self, mode: str) -> "ModelStage":
         """``"fp8"``: the dense projections (qkv, o, gate|up, down) and MoE expert stacks become
         W8A8 e4m3 weights (ops/quant.py); embeddings, norms, router, LM head and the KV cache stay
-        in ``dtype``.  ``"int4"``: the dense projections become W4A16 weights (ops/int4.py), dense Llama only."""
+        in ``dtype``.  ``"int4"``: the dense projections become W4A16 weights (ops/int4.py), dense Llama only; those a
+        4-bit checkpoint brought stay as they are, and no other mode takes such a checkpoint."""
+        check_quantized_checkpoint(self.cfg, mode or "none")
         if mode in ("", "none", None):
             return self
         check_features(self.cfg, quant=mode, tp=self.tp.size)

@@ -174,8 +174,39 @@ def block_to_hf(cfg: ModelConfig, layer: int, w: Dict[str, torch.Tensor]) -> Dic
     return out
 
 
-def hf_to_block(cfg: ModelConfig, layer: int, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """HF-named entries for one block -> runtime (fused) tensors."""
+# the runtime projections of a dense Llama block and the HF modules fused into each, in row order
+W4_PROJECTIONS = {"wqkv": ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "wo": ("self_attn.o_proj",),
+                  "w_gate_up": ("mlp.gate_proj", "mlp.up_proj"), "w_down": ("mlp.down_proj",)}
+
+
+def hf_to_block_w4(cfg: ModelConfig, layer: int, sd: Dict[str, torch.Tensor], device=None) -> Dict[str, object]:
+    """The block of an AWQ / GPTQ 4-bit checkpoint (``cfg.quantization``): every projection's ``qweight`` / ``qzeros``
+    / ``scales`` go to ``device`` and become one fused :class:`ops.int4.Int4Weight`; the norms stay tensors.
+    ``g_idx`` must be the trivial k // 128 (no act-order) and a ``bias`` all zero (GPTQ writers emit both)."""
+    from ..config import check_quantization
+    from ..ops import int4
+    fmt = check_quantization(cfg.quantization)
+    p = f"model.layers.{layer}."
+    out = {"attn_norm": sd[p + "input_layernorm.weight"], "mlp_norm": sd[p + "post_attention_layernorm.weight"]}
+    for name, modules in W4_PROJECTIONS.items():
+        parts = []
+        for m in modules:
+            qw = sd[p + m + ".qweight"]
+            g_idx, bias = sd.get(p + m + ".g_idx"), sd.get(p + m + ".bias")
+            if g_idx is not None and not torch.equal(g_idx.long(), torch.arange(g_idx.numel()) // 128):
+                raise ValueError(f"{p + m}.g_idx is not k // 128: act-order (desc_act) checkpoints are not supported")
+            if bias is not None and bias.count_nonzero():
+                raise ValueError(f"{p + m}.bias is not zero: int4 projections take no bias")
+            parts.append(tuple(sd[p + m + s].to(device) for s in (".qweight", ".qzeros", ".scales")))
+        out[name] = int4.from_checkpoint(parts, fmt)
+    return out
+
+
+def hf_to_block(cfg: ModelConfig, layer: int, sd: Dict[str, torch.Tensor], device=None) -> Dict[str, torch.Tensor]:
+    """HF-named entries for one block -> runtime (fused) tensors.  ``device``: where a 4-bit checkpoint's
+    projections are repacked (:func:`hf_to_block_w4`); plain tensors stay where they are."""
+    if cfg.quantization:
+        return hf_to_block_w4(cfg, layer, sd, device)
     if cfg.arch == "gpt2":
         p = f"transformer.h.{layer}."
         return {

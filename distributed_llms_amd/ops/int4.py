@@ -13,6 +13,12 @@ small batch -- a pure weight stream -- reads a quarter of the bytes.
 * from that M: ``dequant_w4`` into a per-stream scratch tensor and the bf16 route of :func:`..gemm.linear`
   (prefill keeps gemm_pf); the weights are rounded to bf16 once there.
 
+Imported checkpoints (:func:`from_checkpoint`: AWQ "gemm", GPTQ v1 / v2; formats in ops/reference.py): per-group
+zero points 0..15 and f16 (or bf16) scales, w = (code - zero) * scale.  Such a weight keeps one int32 per (row,
+group) -- the scale's f32 bits with the zero in bits 0..3 (csrc/kernels/gemm_w4.hip, "Zero-point variant") -- and
+runs the zero-point instantiations of the same kernels; ``w4_repack`` (csrc/kernels/w4_repack.hip) turns the
+checkpoint's K-major words into the fragment order on the device, each projection into its rows of the fused weight.
+
 Opt-in (``EngineConfig.quant = "int4"``): embeddings, norms, the LM head and the KV cache stay bf16.  The result
 is always dense (``defer`` is accepted and ignored), SwiGLU is ``ops.silu_mul`` on it.  CPU tensors take the
 reference (same codes and scales, f32 math)."""
@@ -61,19 +67,38 @@ def unpack(packed: torch.Tensor) -> torch.Tensor:
 
 
 class Int4Weight:
-    """An [N, K] weight as fragment-packed 4-bit codes ``packed`` (uint8 [N / 16, K / 128, 1024]) and bf16 group
-    scales ``scale`` ([N / 16, K / 128, 16]): w ~= (code - 8) * scale."""
+    """An [N, K] weight as fragment-packed 4-bit codes ``packed`` (uint8 [N / 16, K / 128, 1024]) and, per (row,
+    group) in [N / 16, K / 128, 16] order, either
 
-    __slots__ = ("packed", "scale")
+    * symmetric (round-to-nearest at load): bf16 ``scale``, w ~= (code - 8) * scale; or
+    * with zero points (imported checkpoints): ``sz`` int32, the f32 bits of an f16 / bf16 scale | the zero 0..15,
+      w = (code - zero) * scale.  ``scale`` is then None; :meth:`scales` / :meth:`zeros` give both back.
+
+    ``Int4Weight(packed, scale)`` with a bf16 scale is the symmetric weight; with ``zeros`` (uint8, the scale's shape)
+    or an f16 scale (zeros absent: 8) the two are fused into ``sz``; an int32 ``scale`` is taken as ``sz`` itself, of
+    ``scale_dtype`` scales."""
+
+    __slots__ = ("packed", "scale", "sz", "scale_dtype")
     takes_fp8_act = False        # W4A16: activations stay bf16
 
-    def __init__(self, packed: torch.Tensor, scale: torch.Tensor):
+    def __init__(self, packed: torch.Tensor, scale: torch.Tensor, zeros: Optional[torch.Tensor] = None,
+                 scale_dtype: torch.dtype = torch.float16):
         if packed.dtype != torch.uint8 or packed.dim() != 3 or packed.shape[2] != 1024 or packed.shape[0] % 8 \
-                or scale.dtype != torch.bfloat16 or scale.shape != (*packed.shape[:2], 16) \
-                or scale.device != packed.device:
-            raise ValueError("Int4Weight: packed uint8 [N / 16, K / 128, 1024] (N % 128 == 0) and scale bf16 "
-                             "[N / 16, K / 128, 16] on one device")
-        self.packed, self.scale = packed.contiguous(), scale.contiguous()
+                or scale.dtype not in (torch.bfloat16, torch.float16, torch.int32) \
+                or scale.shape != (*packed.shape[:2], 16) or scale.device != packed.device:
+            raise ValueError("Int4Weight: packed uint8 [N / 16, K / 128, 1024] (N % 128 == 0) and scale bf16 / f16 "
+                             "(or int32 scale | zero) [N / 16, K / 128, 16] on one device")
+        if zeros is not None and (scale.dtype == torch.int32 or zeros.dtype != torch.uint8
+                                  or zeros.shape != scale.shape or zeros.device != scale.device):
+            raise ValueError("Int4Weight: zeros uint8 of the scale's shape and device, next to a bf16 / f16 scale")
+        self.packed, self.scale, self.sz, self.scale_dtype = packed.contiguous(), None, None, scale.dtype
+        if scale.dtype == torch.int32:
+            self.sz, self.scale_dtype = scale.contiguous(), scale_dtype
+        elif zeros is None and scale.dtype == torch.bfloat16:
+            self.scale = scale.contiguous()
+        else:
+            z = torch.full_like(scale, 8, dtype=torch.int32) if zeros is None else zeros.to(torch.int32)
+            self.sz = (scale.float().contiguous().view(torch.int32) & ~15) | z
 
     @property
     def shape(self):
@@ -91,17 +116,30 @@ class Int4Weight:
         return 2 * self.packed.numel()
 
     def nbytes(self) -> int:
-        return self.packed.numel() + 2 * self.scale.numel()
+        return self.packed.numel() + (2 * self.scale.numel() if self.sz is None else 4 * self.sz.numel())
+
+    def to(self, device) -> "Int4Weight":
+        return Int4Weight(self.packed.to(device), (self.scale if self.sz is None else self.sz).to(device),
+                          scale_dtype=self.scale_dtype)
+
+    def _plain(self, t: torch.Tensor) -> torch.Tensor:
+        return t.permute(0, 2, 1).reshape(self.shape[0], -1)
 
     def codes(self) -> torch.Tensor:
         return unpack(self.packed)
 
     def scales(self) -> torch.Tensor:
-        """Scales in plain [N, K / 128] order."""
-        return self.scale.permute(0, 2, 1).reshape(self.shape[0], -1)
+        """Scales in plain [N, K / 128] order (bf16, or the imported checkpoint's f16)."""
+        if self.sz is None:
+            return self._plain(self.scale)
+        return self._plain((self.sz & ~15).view(torch.float32).to(self.scale_dtype))
+
+    def zeros(self) -> Optional[torch.Tensor]:
+        """Zero points in plain [N, K / 128] order (uint8); None for the symmetric weight (8 everywhere)."""
+        return None if self.sz is None else self._plain((self.sz & 15).to(torch.uint8))
 
     def dequantize(self, dtype=torch.float32) -> torch.Tensor:
-        return ref.dequantize_w4(self.codes(), self.scales()).to(dtype)
+        return ref.dequantize_w4(self.codes(), self.scales(), self.zeros()).to(dtype)
 
     def linear(self, x, bias=None, defer: bool = False, swiglu: bool = False):
         """What ops.linear / ops.linear_swiglu do with this weight: always dense, SwiGLU as silu_mul on the result."""
@@ -114,13 +152,64 @@ class Int4Weight:
         return y
 
     def __repr__(self):
-        return f"Int4Weight(shape={tuple(self.shape)}, device={self.device})"
+        return f"Int4Weight(shape={tuple(self.shape)}, device={self.device}, zeros={self.sz is not None})"
 
 
-def from_codes(u: torch.Tensor, s: torch.Tensor) -> Int4Weight:
-    """Codes [N, K] uint8 and scales [N, K / 128] bf16 -> the packed weight."""
+def from_codes(u: torch.Tensor, s: torch.Tensor, z: Optional[torch.Tensor] = None) -> Int4Weight:
+    """Codes [N, K] uint8, scales [N, K / 128] (bf16; f16 or with ``z``: the zero-point weight) and zero points
+    [N, K / 128] uint8 -> the packed weight."""
     t, g = _tiles(*u.shape)
-    return Int4Weight(pack(u), s.view(t, 16, g).permute(0, 2, 1).contiguous())
+    tile = lambda a: a.view(t, 16, g).permute(0, 2, 1).contiguous()
+    return Int4Weight(pack(u), tile(s), None if z is None else tile(z))
+
+
+FORMATS = {"awq": 0, "gptq": 1, "gptq_v2": 2}      # w4_repack's format argument
+
+
+def from_checkpoint(parts, fmt: str) -> Int4Weight:
+    """One weight from the ``(qweight, qzeros, scales)`` of projections stacked along N (q|k|v, gate|up), as an AWQ
+    ("awq") or GPTQ ("gptq": zero - 1 stored, "gptq_v2") checkpoint holds them (ops/reference.py).  On the GPU each
+    part is repacked by ``w4_repack`` into its rows of the weight; on the CPU by the torch unpackers and :func:`pack`."""
+    if fmt not in FORMATS or not parts:
+        raise ValueError(f"from_checkpoint: format {fmt!r} {tuple(FORMATS)} and at least one projection")
+    dev, sdt, shapes = parts[0][0].device, parts[0][2].dtype, []
+    for qw, qz, sc in parts:
+        k, n = (qw.shape[0], 8 * qw.shape[1]) if fmt == "awq" else (8 * qw.shape[0], qw.shape[1])
+        _tiles(n, k)
+        if qw.dtype != torch.int32 or qz.dtype != torch.int32 or sc.dtype != sdt \
+                or sdt not in (torch.float16, torch.bfloat16) or qz.shape != (k // GROUP, n // 8) \
+                or sc.shape != (k // GROUP, n) or not qw.device == qz.device == sc.device == dev:
+            raise ValueError(f"from_checkpoint ({fmt}): qweight int32 {tuple(qw.shape)} needs qzeros int32 "
+                             f"[{k // GROUP}, {n // 8}] and scales f16 / bf16 [{k // GROUP}, {n}] on one device, got "
+                             f"{qz.dtype} {tuple(qz.shape)}, {sc.dtype} {tuple(sc.shape)}")
+        shapes.append((n, k))
+    k = shapes[0][1]
+    if any(kk != k for _, kk in shapes):
+        raise ValueError(f"from_checkpoint: projections of different K {shapes}")
+    if dev.type != "cuda":
+        u, z, s = (torch.cat(a, 0) for a in zip(*(ref.unpack_w4(fmt, *p) for p in parts)))
+        return from_codes(u, s, z)
+    total = sum(n for n, _ in shapes)
+    packed = torch.empty(total // 16, k // GROUP, 1024, dtype=torch.uint8, device=dev)
+    w = Int4Weight(packed, torch.empty(total // 16, k // GROUP, 16, dtype=torch.int32, device=dev), scale_dtype=sdt)
+    row0 = 0
+    for (n, _), p in zip(shapes, parts):
+        repack_into(w, row0, *p, fmt)
+        row0 += n
+    return w
+
+
+def repack_into(w: Int4Weight, row0: int, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
+                fmt: str) -> None:
+    """``w4_repack``: one checkpoint projection into rows ``row0 ..`` of the zero-point weight ``w`` (GPU)."""
+    k, n = (qweight.shape[0], 8 * qweight.shape[1]) if fmt == "awq" else (8 * qweight.shape[0], qweight.shape[1])
+    if w.sz is None or k != w.shape[1] or scales.dtype != w.scale_dtype or not w.device.type == "cuda" \
+            or qzeros.shape != (k // GROUP, n // 8) or scales.shape != (k // GROUP, n):
+        raise ValueError(f"repack_into: a [{n}, {k}] {scales.dtype} projection into {w!r} of {w.scale_dtype} scales")
+    qweight, qzeros, scales = qweight.contiguous(), qzeros.contiguous(), scales.contiguous()
+    _ext.kernels().w4_repack(w.packed.data_ptr(), w.sz.data_ptr(), qweight.data_ptr(), qzeros.data_ptr(),
+                             scales.data_ptr(), FORMATS[fmt], int(scales.dtype == torch.bfloat16), n, k, w.shape[0],
+                             row0, torch.cuda.current_stream().cuda_stream)
 
 
 def quantize_weight(w: torch.Tensor) -> Int4Weight:
@@ -177,8 +266,8 @@ def dequant(w: Int4Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         return w.dequantize(torch.bfloat16)
     if out is None:
         out = torch.empty(n, k, dtype=torch.bfloat16, device=w.device)
-    _ext.kernels().dequant_w4(out.data_ptr(), w.packed.data_ptr(), w.scale.data_ptr(), n, k,
-                              torch.cuda.current_stream().cuda_stream)
+    _ext.kernels().dequant_w4(out.data_ptr(), w.packed.data_ptr(), (w.scale if w.sz is None else w.sz).data_ptr(), n, k,
+                              int(w.sz is not None), torch.cuda.current_stream().cuda_stream)
     return out
 
 
@@ -193,7 +282,7 @@ def linear_int4(x: torch.Tensor, w: Int4Weight, defer: bool = False, splits_: in
     if x.device != w.device:
         raise ValueError(f"linear_int4: x on {x.device}, w on {w.device}")
     if not x.is_cuda:
-        return ref.linear_w4(x, w.codes(), w.scales())
+        return ref.linear_w4(x, w.codes(), w.scales(), w.zeros())
     from . import _ck
     _ck(x, "linear_int4.x", torch.bfloat16)
     m = x.numel() // k
@@ -206,21 +295,26 @@ def linear_int4(x: torch.Tensor, w: Int4Weight, defer: bool = False, splits_: in
     stream = torch.cuda.current_stream().cuda_stream
     ws = gemm._workspace(x.device, stream)
     s = gemm.ws_splits(splits_, m, n) if splits_ else splits(m, n, k, gemm._cus(x.device))
-    _ext.kernels().gemm_w4a16(y.data_ptr(), x.data_ptr(), w.packed.data_ptr(), w.scale.data_ptr(), ws.data_ptr(),
-                              ws.numel(), m, n, k, s, stream)
+    _ext.kernels().gemm_w4a16(y.data_ptr(), x.data_ptr(), w.packed.data_ptr(),
+                              (w.scale if w.sz is None else w.sz).data_ptr(), ws.data_ptr(), ws.numel(), m, n, k, s,
+                              int(w.sz is not None), stream)
     return y
 
 
 def quantize_layers(layers, keys=QUANT_KEYS) -> int:
     """Replace the dense projections of every layer dict whose N and K are multiples of 128 by
     :class:`Int4Weight` (in place) and reserve the dequant scratch for the largest; returns how many were
-    converted.  Everything else stays as it is."""
+    converted.  A weight that already is one (an imported checkpoint's) counts and stays as it is, as does
+    everything else."""
     count, largest, device = 0, 0, None
     for lw in layers:
         for name in keys:
             t = lw.get(name)
             if isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[0] % 128 == 0 and t.shape[1] % GROUP == 0:
                 lw[name] = quantize_weight(t)
+                count += 1
+                largest, device = max(largest, t.numel()), t.device
+            elif isinstance(t, Int4Weight):
                 count += 1
                 largest, device = max(largest, t.numel()), t.device
     if count and device.type == "cuda":

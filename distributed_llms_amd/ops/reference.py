@@ -471,13 +471,54 @@ def quantize_w4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return u.to(torch.uint8).view(n, k), s
 
 
-def dequantize_w4(u: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
-    """wd [N, K] float32 of codes ``u`` [N, K] and scales ``s`` [N, K / 128]."""
-    return (u.float() - 8.0) * s.float().repeat_interleave(W4_GROUP, dim=1)
+def dequantize_w4(u: torch.Tensor, s: torch.Tensor, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wd [N, K] float32 of codes ``u`` [N, K], scales ``s`` [N, K / 128] (bf16 or f16) and zero points ``z``
+    [N, K / 128] (integers 0..15; None: 8 everywhere)."""
+    zero = 8.0 if z is None else z.float().repeat_interleave(W4_GROUP, dim=1)
+    return (u.float() - zero) * s.float().repeat_interleave(W4_GROUP, dim=1)
 
 
-def linear_w4(x: torch.Tensor, u: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
-    return linear(x.float(), dequantize_w4(u, s)).to(x.dtype)
+def linear_w4(x: torch.Tensor, u: torch.Tensor, s: torch.Tensor, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return linear(x.float(), dequantize_w4(u, s, z)).to(x.dtype)
+
+
+# Imported 4-bit checkpoints (ops/int4.py from_checkpoint, csrc/kernels/w4_repack.hip), group size 128, no act-order:
+#   dequantized:  wd[n, k] = f32(u[n, k] - z[n, k / 128]) * f32(s[n, k / 128]), z an integer 0..15, s f16 (or bf16)
+# What a projection of out_features N and in_features K stores, eight 4-bit values per int32 (value i at bit 4 i):
+#   AWQ, version "gemm":  qweight [K, N / 8]: value i of word [k, c] is u[8 c + AWQ_ORDER[i], k];
+#                         qzeros [K / 128, N / 8]: value i of word [g, c] is z[8 c + AWQ_ORDER[i], g]
+#   GPTQ:                 qweight [K / 8, N]: value i of word [r, n] is u[n, 8 r + i];
+#                         qzeros [K / 128, N / 8]: value i of word [g, c] is z[8 c + i, g] - 1 (mod 16) under
+#                         checkpoint_format "gptq" (the default), z[8 c + i, g] itself under "gptq_v2"
+#   both:                 scales [K / 128, N]: s[n, g] = scales[g, n]
+AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)
+W4_FORMATS = ("awq", "gptq", "gptq_v2")
+
+
+def _nibbles(words: torch.Tensor) -> torch.Tensor:
+    """int32 [..., C] -> uint8 [..., C, 8]: value i of every word."""
+    return ((words.to(torch.int64).unsqueeze(-1) >> torch.arange(0, 32, 4, device=words.device)) & 15).to(torch.uint8)
+
+
+def unpack_awq(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor):
+    """-> (codes u [N, K] uint8, zero points z [N, K / 128] uint8, scales s [N, K / 128])."""
+    inv = torch.tensor(AWQ_ORDER, device=qweight.device).argsort()      # slot of row 8 c + m
+    u = _nibbles(qweight)[..., inv].flatten(1).t().contiguous()
+    z = _nibbles(qzeros)[..., inv].flatten(1).t().contiguous()
+    return u, z, scales.t().contiguous()
+
+
+def unpack_gptq(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor, v2: bool = False):
+    """-> (codes u [N, K] uint8, zero points z [N, K / 128] uint8, scales s [N, K / 128])."""
+    u = _nibbles(qweight).permute(1, 0, 2).flatten(1).contiguous()
+    z = _nibbles(qzeros).flatten(1).t()
+    return u, (z if v2 else (z + 1) & 15).contiguous(), scales.t().contiguous()
+
+
+def unpack_w4(fmt: str, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor):
+    if fmt not in W4_FORMATS:
+        raise ValueError(f"int4 checkpoint format {fmt!r} {W4_FORMATS}")
+    return unpack_awq(qweight, qzeros, scales) if fmt == "awq" else unpack_gptq(qweight, qzeros, scales, fmt == "gptq_v2")
 
 
 # ------------------------------------------------------------------ logit processors

@@ -44,6 +44,8 @@ class ModelConfig:
     # the checkpoint's ``quantization_config`` (an AWQ or GPTQ 4-bit checkpoint, check_quantization); served with
     # EngineConfig.quant = "int4" only
     quantization: Optional[Dict[str, Any]] = None
+    # Mistral / Mixtral ``sliding_window``: a query attends to its last W keys, itself included (0: full causal)
+    sliding_window: int = 0
 
     # ------------------------------------------------------------------ sizes
     @property
@@ -118,6 +120,8 @@ class ModelConfig:
             mt, cls = "qwen2", "Qwen2ForCausalLM"
         else:
             mt, cls = ("mixtral", "MixtralForCausalLM") if self.is_moe else ("llama", "LlamaForCausalLM")
+            if self.sliding_window and not self.is_moe:
+                mt, cls = "mistral", "MistralForCausalLM"
         d = {
             "model_type": mt, "architectures": [cls],
             "vocab_size": self.vocab_size, "hidden_size": self.hidden_size,
@@ -138,6 +142,8 @@ class ModelConfig:
             d["num_experts_per_tok"] = self.experts_per_token
         if self.quantization:
             d["quantization_config"] = dict(self.quantization)
+        if self.sliding_window:
+            d["sliding_window"] = self.sliding_window
         return d
 
     @staticmethod
@@ -185,7 +191,8 @@ class ModelConfig:
             bos_token_id=cfg.get("bos_token_id", 1), eos_token_id=eos,
             attn_bias=mt == "qwen2" or (mt == "qwen3" and bool(cfg.get("attention_bias", False))),
             qk_norm=mt == "qwen3",
-            quantization=dict(cfg["quantization_config"]) if check_quantization(cfg.get("quantization_config")) else None)
+            quantization=dict(cfg["quantization_config"]) if check_quantization(cfg.get("quantization_config")) else None,
+            sliding_window=int(cfg.get("sliding_window") or 0) if mt in ("mistral", "mixtral") else 0)
 
 
 def check_quantization(q: Optional[Dict[str, Any]]) -> Optional[str]:
@@ -277,6 +284,11 @@ PRESETS: Dict[str, ModelConfig] = {
         intermediate_size=14336, num_layers=32, num_heads=32, num_kv_heads=8, head_dim=128,
         max_position=32768, rope_theta=1000000.0, norm_eps=1e-5,
         num_experts=8, experts_per_token=2, bos_token_id=1, eos_token_id=2),
+    "mistral-7b": ModelConfig(          # Mistral-7B-v0.1: sliding-window attention over the last 4096 keys
+        name="mistral-7b", arch="llama", vocab_size=32000, hidden_size=4096,
+        intermediate_size=14336, num_layers=32, num_heads=32, num_kv_heads=8, head_dim=128,
+        max_position=32768, rope_theta=10000.0, norm_eps=1e-5, bos_token_id=1, eos_token_id=2,
+        sliding_window=4096),
     "gpt2-small": ModelConfig(
         name="gpt2-small", arch="gpt2", vocab_size=50257, hidden_size=768,
         intermediate_size=3072, num_layers=12, num_heads=12, num_kv_heads=12, head_dim=64,
@@ -302,6 +314,15 @@ PRESETS: Dict[str, ModelConfig] = {
         name="tiny-llama-d128", arch="llama", vocab_size=1024, hidden_size=512,
         intermediate_size=1024, num_layers=4, num_heads=4, num_kv_heads=1, head_dim=128,
         max_position=2048, rope_theta=500000.0, norm_eps=1e-5, bos_token_id=1, eos_token_id=2),
+    # the tiny-llama shapes with Mistral's sliding window (48 and 80: neither a multiple of the 32-key block)
+    "tiny-mistral-sw": ModelConfig(
+        name="tiny-mistral-sw", arch="llama", vocab_size=512, hidden_size=256,
+        intermediate_size=512, num_layers=4, num_heads=4, num_kv_heads=2, head_dim=64,
+        max_position=1024, rope_theta=500000.0, norm_eps=1e-5, bos_token_id=1, eos_token_id=2, sliding_window=48),
+    "tiny-mistral-sw-d128": ModelConfig(
+        name="tiny-mistral-sw-d128", arch="llama", vocab_size=1024, hidden_size=512,
+        intermediate_size=1024, num_layers=4, num_heads=4, num_kv_heads=1, head_dim=128,
+        max_position=2048, rope_theta=500000.0, norm_eps=1e-5, bos_token_id=1, eos_token_id=2, sliding_window=80),
     "tiny-qwen2": ModelConfig(
         name="tiny-qwen2", arch="llama", vocab_size=512, hidden_size=256,
         intermediate_size=512, num_layers=4, num_heads=4, num_kv_heads=2, head_dim=64,

@@ -36,8 +36,10 @@ CXX = os.environ.get("CXX", "g++")
 # v_permlane swap results, which hipcc (IEEE mode) first quiets with a v_max_f32 x, x, x each --
 # 56 of the prefill loop's 88 max instructions; the kernels never produce a NaN (masked scores are
 # -inf and every subtraction keeps a finite reference), so NaN semantics are dropped for that file
-# lm_head_logprobs.hip: the same for its running row maxima (a logit is never NaN for finite operands)
-FILE_FLAGS = {"attention.hip": ["-fno-honor-nans"], "lm_head_logprobs.hip": ["-fno-honor-nans"]}
+# (attention_swa.hip shares that softmax); lm_head_logprobs.hip: the same for its running row maxima (a logit is
+# never NaN for finite operands)
+FILE_FLAGS = {"attention.hip": ["-fno-honor-nans"], "attention_swa.hip": ["-fno-honor-nans"],
+              "lm_head_logprobs.hip": ["-fno-honor-nans"]}
 
 
 def kernel_flags(src: str):

@@ -55,6 +55,10 @@ PYBIND11_MODULE(_C_kernels, m) {
   m.def("paged_attention_decode_rope", &dllm::paged_attention_decode_rope);
   m.def("paged_attention_prefill", &dllm::paged_attention_prefill);
   m.def("paged_attention_prefill_split", &dllm::paged_attention_prefill_split);
+  m.def("paged_attention_decode_window", &dllm::paged_attention_decode_window);
+  m.def("paged_attention_prefill_window", &dllm::paged_attention_prefill_window);
+  m.def("prefill_window_tile_rows", &dllm::prefill_window_tile_rows);
+  m.def("prefill_window_max", &dllm::prefill_window_max);
   m.def("p2p_inbox_bytes", &dllm::p2p_inbox_bytes);
   m.def("p2p_standin", &dllm::p2p_standin);
   m.def("p2p_host_words", &dllm::p2p_host_words);

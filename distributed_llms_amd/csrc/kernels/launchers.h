@@ -127,6 +127,19 @@ void paged_attention_prefill_split(uintptr_t out, uintptr_t q, uintptr_t k_cache
                                    uintptr_t part_o, uintptr_t part_ml, int batch, int total_tokens, int hq, int hkv,
                                    int d, int block_size, int max_blocks, int max_q_len, int max_ctx, int nsplit,
                                    int split_chunks, float scale, uintptr_t stream);
+// attention_swa.hip: sliding-window attention over a rotated q, the query at position p seeing the keys
+// max(0, p - window + 1) .. p.  Decode: split s walks blocks [s, s + 1) * split_blocks of each sequence's window
+// span (num_splits * split_blocks >= ceil(window / 32) + 1).  Prefill: window <= prefill_window_max(hq / hkv)
+void paged_attention_decode_window(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
+                                   uintptr_t block_tables, uintptr_t seq_lens, uintptr_t part_o, uintptr_t part_ml,
+                                   int batch, int hq, int hkv, int d, int block_size, int max_blocks, int window,
+                                   int num_splits, int split_blocks, float scale, uintptr_t stream);
+int prefill_window_tile_rows(int group);
+int prefill_window_max(int group);
+void paged_attention_prefill_window(uintptr_t out, uintptr_t q, uintptr_t k_cache, uintptr_t v_cache,
+                                    uintptr_t block_tables, uintptr_t cu_seqlens_q, uintptr_t seq_lens, int batch,
+                                    int hq, int hkv, int d, int block_size, int max_blocks, int max_q_len, int window,
+                                    float scale, uintptr_t stream);
 
 long p2p_inbox_bytes(long chunk, int nslots);
 void p2p_standin(uintptr_t src, uintptr_t s_inbox, long s_bytes, uint64_t s_seq0, uintptr_t dst, uintptr_t r_inbox,

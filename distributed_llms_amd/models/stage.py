@@ -178,6 +178,9 @@ class ModelStage:
             self.cos_sin = ref.rope_cos_sin(cfg.head_dim, cfg.max_position, cfg.rope_theta, cfg.rope_scaling,
                                             device=self.device)
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
+        # sliding-window attention (Mistral): a query sees its last ``window`` keys; a window that no position can
+        # outgrow is full causal attention (0)
+        self.window = cfg.sliding_window if 0 < cfg.sliding_window < cfg.max_position else 0
 
     # --------------------------------------------------------------- weights
     @property
@@ -372,7 +375,8 @@ class ModelStage:
         decode kernel reduces itself (any other path materialises it)."""
         cfg = self.cfg
         k_cache, v_cache = self.kv.layer(li)
-        fused = not meta.is_prefill and knobs.K.fused_rope and \
+        win = self.window      # a windowed stage takes the unfused path: the windowed kernels read a rotated q
+        fused = not win and not meta.is_prefill and knobs.K.fused_rope and \
             (isinstance(qkv, ops.gemm.SplitKPartial) or qkv.is_cuda)
         if not fused and isinstance(qkv, ops.gemm.SplitKPartial):
             qkv = qkv.materialize()
@@ -388,7 +392,7 @@ class ModelStage:
             route = ops.prefill_route(meta.seq_lens.shape[0] - nd, self.hq, self.hkv, cfg.head_dim,
                                       meta.max_q_len_p if nd else meta.max_q_len,
                                       (meta.max_ctx_p if nd else meta.max_ctx) or None, meta.block_tables.shape[1],
-                                      allow_rope_in_kernel=not nd and qkv.is_cuda)
+                                      allow_rope_in_kernel=not nd and qkv.is_cuda, window=win)
         if route is not None and route.rope_in_kernel:
             ops.rope_cache_append(qkv, meta.positions, self.cos_sin, k_cache, v_cache, meta.slot_mapping,
                                   self.hq, self.hkv, cfg.head_dim, write_q=False)
@@ -404,18 +408,18 @@ class ModelStage:
             nd = meta.num_decode
             o = torch.empty_like(q)
             ops.paged_attention_decode(q[:nd], k_cache, v_cache, meta.block_tables[:nd], meta.seq_lens[:nd],
-                                       self.scale, max_ctx=meta.max_ctx_d or None, out=o[:nd])
+                                       self.scale, max_ctx=meta.max_ctx_d or None, out=o[:nd], window=win)
             ops.paged_attention_prefill(q[nd:], k_cache, v_cache, meta.block_tables[nd:], meta.cu_seqlens_p,
                                         meta.seq_lens[nd:], self.scale, max_q_len=meta.max_q_len_p, out=o[nd:],
-                                        max_ctx=meta.max_ctx_p or None, route=route)
+                                        max_ctx=meta.max_ctx_p or None, route=route, window=win)
             return o.view(o.shape[0], self.q_size_local)
         if meta.is_prefill:
             o = ops.paged_attention_prefill(q, k_cache, v_cache, meta.block_tables, meta.cu_seqlens_q,
                                             meta.seq_lens, self.scale, max_q_len=meta.max_q_len,
-                                            max_ctx=meta.max_ctx or None, route=route)
+                                            max_ctx=meta.max_ctx or None, route=route, window=win)
         else:
             o = ops.paged_attention_decode(q, k_cache, v_cache, meta.block_tables, meta.seq_lens, self.scale,
-                                           max_ctx=meta.max_ctx or None, workspace=meta.attn_workspace)
+                                           max_ctx=meta.max_ctx or None, workspace=meta.attn_workspace, window=win)
         return o.view(o.shape[0], self.q_size_local)
 
     # Split-K partials handed to the consumer instead of reduced by a separate launch: knobs.defer_qkv (the fused
@@ -498,7 +502,8 @@ class ModelStage:
                 x, residual = self._pre_norm(h, residual, lw, "attn_norm", "wqkv")
                 h = None
                 prep = cfg.attn_bias or cfg.qk_norm
-                carry = self._proj(x, lw, l, "wqkv", meta, defer=knobs.K.defer_qkv and has[1] and not prep)
+                carry = self._proj(x, lw, l, "wqkv", meta,
+                                   defer=knobs.K.defer_qkv and has[1] and not prep and not self.window)
                 if prep:
                     # Qwen2 qkv bias / Qwen3 per-head q, k RMSNorm, in place on the dense projection
                     # output: attention (or the next stage, at a cut) sees prepared qkv

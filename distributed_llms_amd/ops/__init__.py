@@ -235,10 +235,11 @@ def silu_mul(gu: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------- K4 - K7: ops/attention.py
 # (imported here, below the helpers it takes from this module)
 from .attention import (MAX_DECODE_SPLITS, PF_MAX_CHUNKS, PF_SPLIT_MAX_PLAIN_WGS, PF_SPLIT_MAX_Q,  # noqa: E402,F401
-                        PF_SPLIT_MIN_CHUNKS, PF_SPLIT_TARGET_WGS, PREFILL_SPLIT, PrefillRoute, decode_split_plan,
-                        decode_workspace, paged_attention_decode, paged_attention_decode_rope,
-                        paged_attention_prefill, paged_attention_prefill_rope, prefill_attn_version, prefill_route,
-                        prefill_split_eligible, prefill_split_plan, rope_cache_append)
+                        PF_SPLIT_MIN_CHUNKS, PF_SPLIT_TARGET_WGS, PREFILL_SPLIT, PREFILL_WINDOW, PrefillRoute,
+                        decode_split_plan, decode_window_plan, decode_workspace, paged_attention_decode,
+                        paged_attention_decode_rope, paged_attention_prefill, paged_attention_prefill_rope,
+                        prefill_attn_version, prefill_route, prefill_split_eligible, prefill_split_plan,
+                        prefill_window_max, rope_cache_append)
 
 
 # ------------------------------------- K10 and the sampling stage: ops/sampling.py

@@ -70,6 +70,25 @@ def decode_split_plan(batch: int, num_kv_heads: int, max_ctx: int, block_size: i
     return splits, split_len
 
 
+def decode_window_plan(batch: int, num_kv_heads: int, window: int, block_size: int = 32,
+                       target_waves: Optional[int] = None) -> Tuple[int, int]:
+    """(num_splits, split_blocks) for the sliding-window decode kernel.  The splits are window-relative: the
+    span of a sequence of ``ctx`` keys starts at block max(0, ctx - window) // 32 and covers at most
+    ceil(window / 32) + 1 blocks, and split s walks the blocks [s, s + 1) x split_blocks of it.  Chosen as
+    decode_split_plan chooses (about ``target_waves`` waves, at least 2 blocks per split) but from the
+    pow2-bucketed batch x kv-heads and the window alone: no context, no table width.  A graph replayed at a
+    padded batch and the eager path therefore partition every sequence's keys identically and produce the same
+    bits, whatever ``max_ctx`` or the block table's width; two batch buckets agree wherever their plans do."""
+    if window < 1:
+        raise ValueError("window >= 1")
+    target_waves = target_waves or knobs.K.attn_target_waves
+    span = -(-window // block_size) + 1
+    pairs = 1 << max(0, (max(1, batch * num_kv_heads) - 1).bit_length())
+    target = max(1, min(MAX_DECODE_SPLITS, target_waves // pairs))
+    split_blocks = max(2, -(-span // target))
+    return -(-span // split_blocks), split_blocks
+
+
 def _into(out: Optional[torch.Tensor], y: torch.Tensor) -> torch.Tensor:
     if out is None:
         return y
@@ -135,20 +154,47 @@ def _decode(b, q, rope, k_cache, v_cache, block_tables, seq_lens, num_heads, hea
     return out
 
 
+def _decode_window(q, k_cache, v_cache, block_tables, seq_lens, scale, window, workspace, out):
+    """The sliding-window decode kernel (attention_swa.hip) on decode_window_plan's grid."""
+    _ck(k_cache, "k_cache")
+    _ck(v_cache, "v_cache")
+    _ck(block_tables, "block_tables", torch.int32)
+    _ck(seq_lens, "seq_lens", torch.int32)
+    (b, hq, d), hkv, bs = q.shape, k_cache.shape[1], k_cache.shape[2]
+    splits, split_blocks = decode_window_plan(b, hkv, window, bs)
+    out = _out_like(out, (b, hq, d), q.dtype, q.device)
+    po, pml = _partials(workspace, b, hq, d, splits, q.device) if splits > 1 else (0, 0)
+    _ext.kernels().paged_attention_decode_window(out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                                 block_tables.data_ptr(), seq_lens.data_ptr(), po, pml, b, hq, hkv, d, bs,
+                                                 block_tables.shape[1], int(window), splits, split_blocks, float(scale),
+                                                 _stream())
+    return out
+
+
+def _no_window(window: int, what: str) -> None:
+    if window:
+        raise ValueError(f"{what} has no sliding-window form: rope_cache_append, then the unfused call with window=")
+
+
 def paged_attention_decode(q, k_cache, v_cache, block_tables, seq_lens, scale: float,
                            max_ctx: Optional[int] = None, workspace: Optional[tuple] = None,
-                           out: Optional[torch.Tensor] = None):
-    """``out``: write the result there (a contiguous [B, Hq, D] view, e.g. rows of a mixed step)."""
+                           out: Optional[torch.Tensor] = None, window: int = 0):
+    """``out``: write the result there (a contiguous [B, Hq, D] view, e.g. rows of a mixed step).  ``window`` W > 0:
+    sliding-window attention, each query sees its last W keys (its own included); ``max_ctx`` plays no part then."""
+    if window < 0:
+        raise ValueError("window >= 0")
     if not _gpu(q):
-        return _into(out, ref.paged_attention_decode(q, k_cache, v_cache, block_tables, seq_lens, scale))
+        return _into(out, ref.paged_attention_decode(q, k_cache, v_cache, block_tables, seq_lens, scale, window))
     _ck(q, "attn.q")
+    if window:
+        return _decode_window(q, k_cache, v_cache, block_tables, seq_lens, scale, window, workspace, out)
     return _decode(q.shape[0], q, None, k_cache, v_cache, block_tables, seq_lens, q.shape[1], q.shape[2], scale, max_ctx,
                    workspace, out, q.dtype, q.device)
 
 
 def paged_attention_decode_rope(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, block_tables, seq_lens,
                                 num_heads: int, num_kv_heads: int, head_dim: int, scale: float,
-                                max_ctx: Optional[int] = None, workspace: Optional[tuple] = None):
+                                max_ctx: Optional[int] = None, workspace: Optional[tuple] = None, window: int = 0):
     """Decode attention with RoPE + KV-cache append fused in (one launch instead of two): reads the raw
     qkv projection [B, (Hq + 2 Hkv) * D], appends each sequence's new k / v at ``slot_mapping`` and
     attends over the whole context including it.  Same result as ``rope_cache_append`` followed by
@@ -156,6 +202,7 @@ def paged_attention_decode_rope(qkv, positions, cos_sin, k_cache, v_cache, slot_
 
     ``qkv`` may be a :class:`gemm.SplitKPartial`: the kernel then sums the split-K slabs (f32 sums of f16 x 2^-6 slices) itself
     (bit-identical to reducing first), which removes the reduce launch and the bf16 round trip."""
+    _no_window(window, "paged_attention_decode_rope")
     part = qkv if isinstance(qkv, gemm.SplitKPartial) else None
     if part is not None and len(part.shape) != 2:
         raise ValueError("qkv partial must be [B, (Hq + 2 Hkv) * D]")
@@ -182,6 +229,15 @@ PF_SPLIT_MAX_Q = 64          # query rows per sequence up to which the cutover w
 KV_BLOCK = 32              # attention.hip kBS: tokens per KV block, the only size the kernels take
 PF_MAX_CHUNKS = 1024    # attention.hip kPfMaxChunks: the LDS prefill kernels stage <= 32k tokens of block ids
 PF_LDS_VERSIONS = (4, 7, 9)  # the LDS kernels: they take the raw qkv projection and rotate q themselves
+PREFILL_WINDOW = 8           # the sliding-window prefill kernel's version number (attention_swa.hip)
+PF_WINDOW_MAX_IDS = 1024     # attention_swa.hip kWinMaxIds: the block ids one workgroup of it stages in LDS
+
+
+def prefill_window_max(group: int) -> int:
+    """The largest window the sliding-window prefill kernel takes: a workgroup of 4 waves x 2 tiles x 16/G rows
+    walks at most (W + rows - 2) // 32 + 2 chunks, whose ids must fit its LDS list."""
+    rows = 4 * max(1, 16 // group) * 2
+    return (PF_WINDOW_MAX_IDS - 2) * KV_BLOCK - rows + 2
 
 
 def prefill_attn_version(max_q_len: int, head_dim: int) -> int:
@@ -239,7 +295,7 @@ def prefill_split_eligible(batch: int, num_kv_heads: int, max_q_len: int, max_ct
 # ------------------------------------------------------------ prefill: the route
 @dataclass(frozen=True)
 class PrefillRoute:
-    """What one prefill attention call runs.  ``version``: the kernel (3, 4, 5, 7 or 9);
+    """What one prefill attention call runs.  ``version``: the kernel (3, 4, 5, 7 or 9; 8 with a sliding window);
     ``rope_in_kernel``: the kernel reads the raw qkv projection and rotates q itself (the caller appends
     with ``write_q=False`` and calls paged_attention_prefill_rope), else it reads a rotated q; ``nsplit``,
     ``split_chunks``: the plan of version 5 (0, 0 while the longest context is unknown), 1, 0 otherwise."""
@@ -251,7 +307,7 @@ class PrefillRoute:
 
 def prefill_route(batch: int, num_heads: int, num_kv_heads: int, head_dim: int, max_q_len: int,
                   max_ctx: Optional[int], max_blocks: int, *, version: int = 0, nsplit: Optional[int] = None,
-                  allow_rope_in_kernel: bool = True) -> PrefillRoute:
+                  allow_rope_in_kernel: bool = True, window: int = 0) -> PrefillRoute:
     """The route of a prefill call over ``batch`` sequences of at most ``max_q_len`` new rows and ``max_ctx``
     keys (None: unknown to the host) behind block tables ``max_blocks`` wide.  Pure: shapes and knobs in.
     ``version`` forces a kernel; otherwise knobs.prefill_attn == 5 forces the split-context kernel, a call
@@ -259,8 +315,20 @@ def prefill_route(batch: int, num_heads: int, num_kv_heads: int, head_dim: int, 
     kernels (7, 9) exist for head_dim 128 and groups up to 16 (else 4), and the LDS kernels stage at most
     PF_MAX_CHUNKS block ids per sequence (else 3, the register-tiled kernel, which reads a rotated q).
     ``nsplit`` forces version 5's split count (tests, benchmarks; also more splits than chunks, the trailing
-    ones empty).  ``allow_rope_in_kernel=False``: the caller has a rotated q anyway (a mixed step)."""
+    ones empty).  ``allow_rope_in_kernel=False``: the caller has a rotated q anyway (a mixed step).
+    ``window`` > 0: sliding-window attention, always PREFILL_WINDOW over a rotated q -- that kernel stages only
+    the block ids a row tile walks, so neither the context nor the table width bounds it, but the window does
+    (prefill_window_max, else a ValueError)."""
     group = num_heads // num_kv_heads
+    if window:
+        if version not in (0, PREFILL_WINDOW):
+            raise ValueError(f"prefill attention {version} has no sliding-window form")
+        if not 0 < window <= prefill_window_max(group):
+            raise ValueError(f"sliding window {window}: the prefill kernel stages the block ids of at most "
+                             f"{prefill_window_max(group)} keys (GQA group {group})")
+        return PrefillRoute(PREFILL_WINDOW, False)
+    if version == PREFILL_WINDOW:
+        raise ValueError("prefill attention 8 is the sliding-window kernel: pass window=")
     version = version or (PREFILL_SPLIT if knobs.K.prefill_attn == PREFILL_SPLIT else 0)
     if version == PREFILL_SPLIT or (not version and
                                     prefill_split_eligible(batch, num_kv_heads, max_q_len, max_ctx, group)):
@@ -299,7 +367,7 @@ def _prefill_split(out, q, tensors, b, hkv, bs, max_blocks, max_q_len, max_ctx, 
 
 
 def _prefill(src, rope, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, num_heads, head_dim, scale,
-             max_q_len, out, route, version=0, max_ctx=None, nsplit=None, workspace=None):
+             max_q_len, out, route, version=0, max_ctx=None, nsplit=None, workspace=None, window=0):
     """Both prefill wrappers.  ``rope``: None (``src`` is the rotated q [T, Hq, D]) or (positions, cos_sin)
     with ``src`` the raw qkv projection [T, (Hq + 2 Hkv) * D]."""
     _ck(k_cache, "k_cache")
@@ -315,7 +383,9 @@ def _prefill(src, rope, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, 
     max_q_len = int(max_q_len)
     if route is None:
         route = prefill_route(b, hq, hkv, d, max_q_len, max_ctx, max_blocks, version=version, nsplit=nsplit,
-                              allow_rope_in_kernel=rope is not None)
+                              allow_rope_in_kernel=rope is not None, window=window)
+    if (route.version == PREFILL_WINDOW) != bool(window):
+        raise ValueError("the prefill route and window= disagree: PREFILL_WINDOW is the route of a windowed call")
     if route.rope_in_kernel != (rope is not None):
         raise ValueError("in-kernel prefill RoPE needs an LDS prefill kernel (knobs.prefill_attn 0, 4, 7 or 9) and "
                          f"block tables of <= {PF_MAX_CHUNKS} blocks; the other kernels read a rotated q")
@@ -325,6 +395,11 @@ def _prefill(src, rope, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, 
             return out
         return _prefill_split(out, src, tensors, b, hkv, bs, max_blocks, max_q_len, max_ctx, scale, route, nsplit,
                               workspace)
+    if route.version == PREFILL_WINDOW:
+        _ext.kernels().paged_attention_prefill_window(out.data_ptr(), src.data_ptr(), *(x.data_ptr() for x in tensors),
+                                                      b, hq, hkv, d, bs, max_blocks, max_q_len, int(window),
+                                                      float(scale), _stream())
+        return out
     positions, cos_sin = rope or (None, None)
     _ext.kernels().paged_attention_prefill(out.data_ptr(), src.data_ptr(), *(x.data_ptr() for x in tensors), b, hq, hkv,
                                            d, bs, max_blocks, max_q_len, float(scale), route.version,
@@ -337,27 +412,33 @@ def _prefill(src, rope, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, 
 def paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, scale: float,
                             max_q_len: Optional[int] = None, version: int = 0, out: Optional[torch.Tensor] = None,
                             max_ctx: Optional[int] = None, nsplit: Optional[int] = None,
-                            workspace: Optional[tuple] = None, route: Optional[PrefillRoute] = None):
+                            workspace: Optional[tuple] = None, route: Optional[PrefillRoute] = None,
+                            window: int = 0):
     """Prefill attention over a rotated q [T, Hq, D].  ``route``: the call's prefill_route where the caller
     has it; otherwise built here from ``version`` (prefill kernel 3, 4, 5, 7 or 9; 0: the default),
     ``nsplit`` and ``max_ctx`` -- the batch's longest context, known to the host.  ``out`` as
     paged_attention_decode.  Version 5 is the split-context kernel (every row of q must belong to a
-    sequence): ``workspace`` its (o, ml) partial buffers (None: allocated for the call)."""
+    sequence): ``workspace`` its (o, ml) partial buffers (None: allocated for the call).  ``window`` W > 0:
+    sliding-window attention (the query at position p sees the keys p - W + 1 .. p) on the windowed kernel."""
+    if window < 0:
+        raise ValueError("window >= 0")
     if not _gpu(q):
         return _into(out, ref.paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens,
-                                                      scale))
+                                                      scale, window))
     _ck(q, "attn.q")
     return _prefill(q, None, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens, q.shape[1], q.shape[2], scale,
-                    max_q_len, out, route, version, max_ctx, nsplit, workspace)
+                    max_q_len, out, route, version, max_ctx, nsplit, workspace, window)
 
 
 def paged_attention_prefill_rope(qkv, positions, cos_sin, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens,
                                  num_heads: int, head_dim: int, scale: float, max_q_len: Optional[int] = None,
-                                 out: Optional[torch.Tensor] = None, route: Optional[PrefillRoute] = None):
+                                 out: Optional[torch.Tensor] = None, route: Optional[PrefillRoute] = None,
+                                 window: int = 0):
     """Prefill attention reading q straight from the qkv projection [T, (Hq + 2 Hkv) * D] and rotating it
     in registers (K / V already appended by ``rope_cache_append(..., write_q=False)``): the rotated q
     never round-trips through HBM.  Returns [T, Hq, D].  ``route`` as paged_attention_prefill; it must
     say ``rope_in_kernel``."""
+    _no_window(window, "paged_attention_prefill_rope")
     if not _gpu(qkv):
         q = ref.rope_q(qkv, positions, cos_sin, num_heads, head_dim)
         return _into(out, ref.paged_attention_prefill(q, k_cache, v_cache, block_tables, cu_seqlens_q, seq_lens,

@@ -185,8 +185,9 @@ def _gather_kv(k_cache, v_cache, block_table, n):
 
 def paged_attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                            block_tables: torch.Tensor, seq_lens: torch.Tensor,
-                           scale: float) -> torch.Tensor:
+                           scale: float, window: int = 0) -> torch.Tensor:
     """q [B, Hq, D] (one new token per sequence, already in the cache) -> [B, Hq, D].
+    ``window`` W > 0: sliding-window attention, the query at position len - 1 sees its last W keys.
 
     The whole batch in one gather: every sequence's first ceil(max_len / bs) blocks (table
     padding is block 0, a valid index), keys past its own length masked to -inf.
@@ -208,7 +209,10 @@ def paged_attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
     k = kb.permute(0, 2, 1, 3, 4).reshape(b, hkv, nb * bs, d)
     qf = q.float().view(b, hkv, hq // hkv, d)
     s = torch.einsum("bhgd,bhnd->bhgn", qf, k.float()) * scale
-    pad = torch.arange(nb * bs, device=q.device).view(1, 1, 1, -1) >= lens.to(q.device).view(b, 1, 1, 1)
+    kpos = torch.arange(nb * bs, device=q.device).view(1, 1, 1, -1)
+    pad = kpos >= lens.to(q.device).view(b, 1, 1, 1)
+    if window > 0:
+        pad = pad | (kpos < lens.to(q.device).view(b, 1, 1, 1) - window)
     p = torch.softmax(s.masked_fill(pad, float("-inf")), dim=-1)
     o = torch.einsum("bhgn,bhnd->bhgd", p, v.float())
     return o.reshape(b, hq, d).to(q.dtype)
@@ -216,8 +220,9 @@ def paged_attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
 
 def paged_attention_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                             block_tables: torch.Tensor, cu_seqlens_q: torch.Tensor,
-                            seq_lens: torch.Tensor, scale: float) -> torch.Tensor:
-    """Causal varlen attention for a packed chunk of prompts.
+                            seq_lens: torch.Tensor, scale: float, window: int = 0) -> torch.Tensor:
+    """Causal varlen attention for a packed chunk of prompts.  ``window`` W > 0: sliding-window attention,
+    the query at position p sees the keys p - W + 1 .. p.
 
     q [T, Hq, D]; sequence i owns q rows cu_seqlens_q[i]:cu_seqlens_q[i+1], which are its
     LAST q_len tokens out of seq_lens[i] context tokens (all already in the cache).
@@ -238,6 +243,8 @@ def paged_attention_prefill(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
         qpos = torch.arange(n - ql, n, device=q.device).view(ql, 1)
         kpos = torch.arange(n, device=q.device).view(1, n)
         s = s.masked_fill(kpos > qpos, float("-inf"))
+        if window > 0:
+            s = s.masked_fill(kpos <= qpos - window, float("-inf"))
         p = torch.softmax(s, dim=-1)
         o = torch.einsum("hgqn,hnd->hgqd", p, v.float())
         out[s0:s1] = o.reshape(hq, ql, d).permute(1, 0, 2).to(q.dtype)
